@@ -15,6 +15,12 @@ Workload = BASELINE.json configs[2]: TFIM g=1, D=4, B=65536 Haar-random state un
                one left in the 256 MiB Infinity Cache (default: the smallest R with R x batch bytes > 256 MiB).
   --scaling    weak: --batch evaluations per GPU (default);  strong: --batch is the GLOBAL batch, rank r
                evaluates the contiguous shard qmps_amd.dist.shard_bounds(B, r, N)  (B/G per GPU).
+  --full       energy workload: everything beyond the headline figure as well - CPU baselines, the 15 repeated blocks,
+               the informational legs after the timed region and (N = 1) `other_configs`.  A plain run only sets up,
+               warms up, times the --steps steps and prints the line.
+  --dump-outputs DIR   energy workload: after the timed steps, what the last timed step computed (rank 0's batch:
+               energies, iteration counts, statuses, summed cost) as DIR/<name>.npy in float64; the inputs are fixed
+               by --seed, so two builds can be compared output for output.
 
 The product path uses no PyTorch: kernels, streams, events and the RCCL communicator live in libqmps_hip.so
 (ctypes).  For N > 1 torch.distributed (gloo, CPU) is launcher plumbing only: rendezvous, the barriers around
@@ -41,7 +47,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 # inputs, byte / flop counts, CPU baselines, launcher plumbing (benchlib/common.py) and the three other workloads; THIS file is the
-# command line, the headline energy workload with its timed region (main), and the other_configs leg of the default run
+# command line, the headline energy workload with its timed region (main), and the other_configs leg of a --full run
 from benchlib.common import *  # noqa: E402,F401,F403
 from benchlib.common import FP64_PEAK_TFLOPS, HBM_PEAK_GBPS, MALL_MIB, ROOT, _one_blas_thread, _ref_chunk  # noqa: E402,F401
 from benchlib.overlap import main_overlap, nearby_tensors  # noqa: E402,F401
@@ -103,6 +109,27 @@ def other_configs(args, budget_s=60.0):
                    'config 4 carries the inverse Hessians between time steps (`identity_start`: scipy\'s / the reference\'s restart from the identity)')
     res['wall_s'] = time.perf_counter() - t0
     return res
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirname, per_eval, whole):
+    """--dump-outputs: every array as DIR/<name>.npy in float64.  per_eval = arrays whose first axis is the evaluation; beyond
+    64 MB in all they are cut to a fixed, seeded sample of evaluations (the same rows in every array, listed in sample_index.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in whole.items()}
+    per_eval = {k: np.asarray(v, dtype=np.float64) for k, v in per_eval.items()}
+    n = min(len(v) for v in per_eval.values())
+    row_bytes = sum(v[0].nbytes for v in per_eval.values()) + 8
+    room = DUMP_MAX_BYTES - sum(v.nbytes for v in out.values())
+    if n * row_bytes > room:
+        idx = np.sort(np.random.default_rng(0).choice(n, room // row_bytes, replace=False))
+        per_eval = {k: v[idx] for k, v in per_eval.items()}
+        out['sample_index'] = idx.astype(np.float64)
+    out.update(per_eval)
+    for k, v in out.items():
+        np.save(os.path.join(dirname, f'{k}.npy'), v)
 
 
 def main():
@@ -167,13 +194,22 @@ def main():
                     help='N > 1: the summed costs of this many steps travel in one RCCL all-reduce (1 = an exchange per step, the '
                          'headline; a grouped figure is printed as an extra)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-repeats', action='store_true', help='energy workload: time the --steps block once (default: 16 blocks, median / min / max reported beside `value`)')
+    ap.add_argument('--no-repeats', action='store_true', help='energy workload: time the --steps block once (--full otherwise runs 16 blocks, median / min / max reported beside `value`)')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='energy workload, N = 1: skip the `other_configs` extra (BASELINE.json configs[1], [3], [4] as their own optimiser workloads, bounded to ~60 s)')
+                    help='energy workload, N = 1, --full: skip the `other_configs` extra (BASELINE.json configs[1], [3], [4] as their own optimiser workloads, bounded to ~60 s)')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the informational legs that run after the timed region (PCIe-inclusive, ansatz-parameter-inclusive, '
+                    help='skip the informational legs that run after the timed region (the energy workload runs them with --full only; PCIe-inclusive, ansatz-parameter-inclusive, '
                          'contraction-only, grouped exchange): under rocprofv3 the per-kernel averages then cover the timed workload only')
+    ap.add_argument('--full', action='store_true',
+                    help='energy workload: also run what the headline figure does not need - the CPU baselines, the 15 repeated blocks, the '
+                         'informational legs after the timed region and, at N = 1, `other_configs` (--no-cpu-baseline, --no-repeats, '
+                         '--no-extras, --no-other-configs still trim it); the other workloads run as they always did')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='energy workload: write what the last timed step computed (energies, iteration counts, statuses, summed cost of '
+                         'rank 0\'s batch) as DIR/<name>.npy in float64, at most 64 MB (a fixed, seeded sample of the evaluations beyond that)')
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.workload != 'energy':
+        ap.error('--dump-outputs: the energy workload only')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args)
 
@@ -212,7 +248,7 @@ def main():
 
     # CPU baselines first: nothing has touched the GPU yet, so the process pool may fork
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(D, A, h, args.max_iter, args.tol)
 
     dist = None
@@ -262,6 +298,7 @@ def main():
     eng.set_kernel_timing_period(timing_period)
 
     direct = args.solver == 'direct' and D == 4
+    extras_on = args.full and not args.no_extras     # the informational legs after the timed region (rank 0) and the grouped exchange
     store_env = args.store_env or not direct
     accumulate = not (D == 4 and args.solver == 'squaring')      # every path but the two-kernel D = 4 squaring solver
     count = [0]
@@ -304,9 +341,18 @@ def main():
         eng.exchange_stats(reset=True)
     elapsed, ev_ms = timed(args.steps)
     exch = eng.exchange_stats() if dist is not None and rccl_ok else None
-    # the same block of --steps steps again, 15 times (every rank: the blocks carry the barriers and, at N > 1, the exchanges of the
+    if args.dump_outputs is not None:
+        # what the last timed step handed back: the summed cost (every rank: with a grouped exchange reading it closes the open
+        # group, a collective call) and, on rank 0, its window's energies / iteration counts / statuses
+        cost_last = eng.get_cost()
+        if rank == 0:
+            eng.set_window(((count[0] - 1) % R) * B)
+            E_last, it_last, st_last = eng.results(B)
+            eng.set_window(0)
+            dump_outputs(args.dump_outputs, {'energies': E_last, 'iterations': it_last, 'status': st_last}, {'summed_cost': cost_last})
+    # --full: the same block of --steps steps again, 15 times (every rank: the blocks carry the barriers and, at N > 1, the exchanges of the
     # first): `value` stays the FIRST block's (the contract's K timed steps); median / min / max of all 16 are reported beside it
-    block_s = [elapsed] + [timed(args.steps)[0] for _ in range(0 if args.no_repeats else 15)]
+    block_s = [elapsed] + [timed(args.steps)[0] for _ in range(15 if args.full and not args.no_repeats else 0)]
 
     cost = eng.get_cost()
     if dist is not None and not rccl_ok:
@@ -326,7 +372,7 @@ def main():
     eng.set_window(0)
 
     extras = {}
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras_on:
         # PCIe-inclusive rate (never `value`): host tensors in, energies out through the one-shot entry point
         eng.set_solver(args.solver, handoff=args.handoff if args.handoff is not None else eng.handoff)
         eng.energies(A, h, max_iter=args.max_iter, tol=args.tol)
@@ -413,7 +459,7 @@ def main():
                 'flops_per_eval': 1920 + 5040, 'working_set_mib': R * B * 48 * D * D / 2 ** 20,
                 'what': 'QMPS_FLAG_WARM_RESIDENT: the resident (converged) environment of every evaluation is accepted by one power step; '
                         f'no matrix build, no elimination; reads tensor + environment ({48 * D * D + 8} B per evaluation), cycled over the {R} resident batches'}
-    if rank == 0 and not args.no_extras and D <= 8:
+    if rank == 0 and extras_on and D <= 8:
         # BASELINE.json configs[2] says "power-iteration environment solve": the same step with the iterative solvers on the
         # record (QMPS_ENV_POWER = the reference's krylov / PowerCircuit, QMPS_ENV_POWER_SQUARING = the same 2^m steps at a time);
         # same fixed point, same tolerance as the direct solve of the headline.  No cost exchange in this rank-0-only leg.
@@ -449,7 +495,7 @@ def main():
         legs['what'] = ('the same resident batches, environment by power iteration to the same tolerance: "plain" = normalised power '
                         'iteration (krylov / PowerCircuit of the reference), "squaring" = 2^m power steps at a time; energies stored, no cost sum')
         extras['power_iteration'] = legs
-    if dist is not None and rccl_ok and not args.no_extras and args.exchange_every == 1:
+    if dist is not None and rccl_ok and extras_on and args.exchange_every == 1:
         # the grouped exchange (16 steps' costs per all-reduce) as an extra, every rank takes part
         eng.set_tensors(A_all)
         eng.set_exchange_period(16)
@@ -461,7 +507,7 @@ def main():
         extras['grouped_exchange_16'] = {'evals_per_s': global_batch * n16 / el16,
                                          'what': 'same steps, the summed costs of 16 consecutive steps per all-reduce'}
 
-    if rank == 0 and world == 1 and dist is None and not args.no_extras and not args.no_other_configs and (D, args.batch) == (4, 65536):
+    if rank == 0 and world == 1 and dist is None and extras_on and not args.no_other_configs and (D, args.batch) == (4, 65536):
         extras['other_configs'] = other_configs(args)
     tot = np.array([float(iters.sum()), float((status != 0).sum()), float((iters > 1).sum()), float(len(iters))])
     if dist is not None:
@@ -545,7 +591,7 @@ def main():
         out['value_median'] = out['repeats']['value_median']
         out.update(exchange_report(world, ms_per_step, kernel_ms, value, None if exch is None else float(exch[2]), args.steps,
                                    (extras.get('grouped_exchange_16') or {}).get('evals_per_s')))
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu
         emit(args, out)
 

@@ -72,11 +72,11 @@ def test_grouped_exchange_keeps_every_step_cost(with_comm):
 @pytest.mark.parametrize('scaling', ['weak', 'strong'])
 def test_bench_distributed_code_path_world1(scaling):
     """bench.py's N > 1 branch (gloo rendezvous, unique-id broadcast, RCCL init + ncclCommCount check, one all-reduce
-    per step, the grouped-exchange extra), forced at world size 1 through the same launcher the driver uses."""
+    per step, the grouped-exchange extra of --full), forced at world size 1 through the same launcher the driver uses."""
     env = dict(os.environ, QMPS_BENCH_FORCE_DIST='1', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
            '127.0.0.1', '--master-port', '29517', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3',
-           '--warmup', '1', '--no-cpu-baseline', '--batch', '4096', '--rotate', '3', '--scaling', scaling]
+           '--warmup', '1', '--no-cpu-baseline', '--batch', '4096', '--rotate', '3', '--scaling', scaling, '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     import json
@@ -116,13 +116,13 @@ def test_bench_two_ranks_on_one_device(scaling):
 
 
 def test_bench_two_ranks_with_extras():
-    """The same with the informational legs enabled: the rank-0-only extras must not issue collective calls (round 2's advisor
+    """The same with the informational legs enabled (--full): the rank-0-only extras must not issue collective calls (round 2's advisor
     finding: a cost exchange inside a rank-0-only leg would leave unmatched all-reduces behind)."""
     import json
     env = dict(os.environ, QMPS_BENCH_ONE_DEVICE='1', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
            '127.0.0.1', '--master-port', '29521', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '5',
-           '--warmup', '2', '--no-cpu-baseline', '--batch', '4096', '--rotate', '2']
+           '--warmup', '2', '--no-cpu-baseline', '--batch', '4096', '--rotate', '2', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
@@ -130,13 +130,13 @@ def test_bench_two_ranks_with_extras():
 
 
 def test_bench_extras_with_a_communicator_world1():
-    """Extras enabled WITH a live RCCL communicator (world size 1 through the launcher): the warm-start leg runs without a
+    """Extras enabled (--full) WITH a live RCCL communicator (world size 1 through the launcher): the warm-start leg runs without a
     cost exchange, the run completes and reports it."""
     import json
     env = dict(os.environ, QMPS_BENCH_FORCE_DIST='1', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
            '127.0.0.1', '--master-port', '29523', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5',
-           '--warmup', '2', '--no-cpu-baseline', '--batch', '4096', '--rotate', '2']
+           '--warmup', '2', '--no-cpu-baseline', '--batch', '4096', '--rotate', '2', '--full']
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])

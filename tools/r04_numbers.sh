@@ -4,7 +4,7 @@
 tag=${1:-r04h}
 R=$GRAFT_REPO_ROOT
 o=$R/gpurun_out
-run() { n=$1; shift; timeout 900 python $R/bench.py "$@" > $o/${tag}_$n.json 2> $o/${tag}_$n.err || echo "FAILED $n"; }
+run() { n=$1; shift; timeout 900 python $R/bench.py --full "$@" > $o/${tag}_$n.json 2> $o/${tag}_$n.err || echo "FAILED $n"; }
 run headline --steps 20 --warmup 5
 run d8_b768 --D 8 --batch 768 --steps 400 --warmup 100 --no-cpu-baseline
 run d8_b96 --D 8 --batch 96 --steps 400 --warmup 100 --no-cpu-baseline

@@ -4,7 +4,7 @@
 tag=${1:-r05}
 R=$GRAFT_REPO_ROOT
 o=$R/gpurun_out
-run() { n=$1; shift; timeout 900 python $R/bench.py "$@" > $o/${tag}_$n.json 2> $o/${tag}_$n.err || echo "FAILED $n"; }
+run() { n=$1; shift; timeout 900 python $R/bench.py --full "$@" > $o/${tag}_$n.json 2> $o/${tag}_$n.err || echo "FAILED $n"; }
 run headline
 # single-GPU times of the 8-GPU shards of configs 2, 3, 4 (what a strong-scaled split can gain)
 run d4_b8192 --D 4 --batch 8192 --no-cpu-baseline --no-extras

@@ -4,11 +4,11 @@
 tag=${1:-r06}
 R=$GRAFT_REPO_ROOT
 o=$R/gpurun_out
-run() { n=$1; shift; timeout 900 python $R/bench.py "$@" > $o/${tag}_$n.json 2> $o/${tag}_$n.err || echo "FAILED $n"; }
+run() { n=$1; shift; timeout 900 python $R/bench.py --full "$@" > $o/${tag}_$n.json 2> $o/${tag}_$n.err || echo "FAILED $n"; }
 run headline
 # BASELINE configs[2] read literally: the same step with the power-iteration environment solves (plain = env_power_d4_kernel of round 6)
 run d4_plain --solver plain --steps 200 --warmup 20 --no-cpu-baseline --no-extras
-QMPS_POWER_LANE=1 timeout 900 python $R/bench.py --solver plain --steps 60 --warmup 10 --no-cpu-baseline --no-extras > $o/${tag}_d4_plain_lane.json 2> $o/${tag}_d4_plain_lane.err
+QMPS_POWER_LANE=1 timeout 900 python $R/bench.py --full --solver plain --steps 60 --warmup 10 --no-cpu-baseline --no-extras > $o/${tag}_d4_plain_lane.json 2> $o/${tag}_d4_plain_lane.err
 run d4_squaring --solver squaring --steps 400 --warmup 50 --no-cpu-baseline --no-extras
 # single-GPU times of the 8-GPU shards of configs 2, 3, 4 (what a strong-scaled split can gain)
 run d4_b8192 --D 4 --batch 8192 --no-cpu-baseline --no-extras
