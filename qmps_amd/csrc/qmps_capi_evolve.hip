@@ -241,13 +241,12 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
   auto dev_gradient = [&](const double* d_src, const unsigned char* mask) -> int {
     HIP_TRY(qmps::launch_ansatz(c->D, kind, d_src, P, c->d_A, T, c->stream));      // (every row: a masked-out row's tensor is never read)
     if (beside_dev && !fused_probe_dev) HIP_TRY(hipEventRecord(c->aux_fork, c->stream));      // (the second stream builds the neighbours' tensors)
-    c->timed = per_eval;
-    const int tslot = (int)(c->samples % qmps_ctx::kRing);
-    if (c->timed) HIP_TRY(hipEventRecord(c->kev0[tslot], c->stream));
+    KernelTimer timer(c, per_eval);
+    HIP_TRY(timer.start());
     c->dominant = c->D == 16 ? "overlap_mfma_d16_kernel + adjoint + neighbour probes" : "overlap solve + adjoint + neighbour probes";
     GradPass gp;
     if (int e = enqueue_gradient_kernels(c, T, kind, P, d_src, h, grad_rounds, grad_tol, warm, true, mask, beside_dev, false, gp, adaptive ? dv.tolarr : nullptr)) return e;
-    if (c->timed) { HIP_TRY(hipEventRecord(c->kev1[tslot], c->stream)); c->samples++; }
+    HIP_TRY(timer.stop());
     c->launches++;
     warm = true;
     c->grad_warm_T = T;

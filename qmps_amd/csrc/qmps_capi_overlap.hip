@@ -44,24 +44,22 @@ int arm_queue(qmps_ctx* c, qmps::OverlapArgs& a, int which) {
   a.queue = nullptr;
   if (c->D != 16 || a.B <= 2048 || documented_switch("QMPS_D16_ONE_WAVE") != nullptr || documented_switch("QMPS_D16_BLOCK") != nullptr) return QMPS_OK;
   if (!c->d_queue) return fail(QMPS_ERR_STATE, "overlap work counters not allocated (ensure_overlap_outputs)");
-  HIP_TRY(hipMemsetAsync(c->d_queue + which, 0, sizeof(int), c->stream));
-  a.queue = c->d_queue + which;
+  a.queue = c->d_queue + qmps_ctx::kOverlapQueue + which;
+  HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(int), c->stream));
   return QMPS_OK;
 }
 // D = 8, 16: arm the Krylov fall-back of a power launch (include/qmps_hip.h "fixed-point solvers"): the power kernel hands a
-// candidate over once its residual history predicts more than kKrylovAfter further steps.  QMPS_NO_KRYLOV: plain power method.
-constexpr int kKrylovAfter = 256;
+// candidate over once its residual history predicts more than krylov_after() further steps.  QMPS_NO_KRYLOV: plain power method.
 int arm_krylov(qmps_ctx* c, qmps::OverlapArgs& a, int which) {
   a.krylov_after = 0;
   a.kry_counter = nullptr;
   if (c->D < 8 || documented_switch("QMPS_NO_KRYLOV") != nullptr || documented_switch("QMPS_D16_ONE_WAVE") != nullptr || documented_switch("QMPS_D16_BLOCK") != nullptr) return QMPS_OK;
   if (!c->d_queue || !c->d_kry) return fail(QMPS_ERR_STATE, "Krylov fall-back buffers not allocated (ensure_overlap_outputs)");
-  int after = kKrylovAfter;
-  if (const char* e = tuning_knob("QMPS_KRYLOV_AFTER")) after = atoi(e);
+  const int after = krylov_after();
   if (after <= 0) return QMPS_OK;
   if (a.r_out == nullptr) a.r_out = (char*)c->d_kry + (size_t)c->window * env_bytes(c);     // (the iterate travels through r_out)
   a.krylov_after = after;
-  a.kry_counter = c->d_queue + 2 + 3 * which;
+  a.kry_counter = c->d_queue + qmps_ctx::kOverlapKrylov + 3 * which;
   return QMPS_OK;
 }
 
@@ -74,13 +72,12 @@ int launch_overlap_kernels(qmps_ctx* c, const qmps::OverlapArgs& a_in) {
   const bool squaring = overlap_squares(c);
   c->dominant = c->D == 2 ? "overlap_lane_kernel" : (c->D == 4 && squaring ? "overlap_square_d4_kernel" :
                 (c->D == 16 && !documented_switch("QMPS_D16_BLOCK") ? "overlap_mfma_d16_kernel" : "overlap_block_kernel<D>"));
-  c->timed = !c->capturing && c->timing_period > 0 && c->launches % c->timing_period == 0;
-  const int slot = (int)(c->samples % qmps_ctx::kRing);
-  if (c->timed) HIP_TRY(hipEventRecord(c->kev0[slot], c->stream));
+  KernelTimer timer(c, periodic_timing(c));
+  HIP_TRY(timer.start());
   a.no_deflation = documented_switch("QMPS_NO_DEFLATION") != nullptr ? 1 : 0;
   if (c->D == 2) HIP_TRY(qmps::launch_overlap(a, c->stream));
   else HIP_TRY(qmps::launch_overlap_d(c->D, a, c->D == 4 ? squaring : documented_switch("QMPS_D16_BLOCK") == nullptr, c->stream));
-  if (c->timed) { HIP_TRY(hipEventRecord(c->kev1[slot], c->stream)); c->samples++; }
+  HIP_TRY(timer.stop());
   if (!c->capturing) c->launches++;
   return QMPS_OK;
 }
@@ -528,9 +525,8 @@ int qmps_overlap_gradient(qmps_ctx* c, int64_t T, int kind, int n_params, const 
   }
   // HIP events around the WHOLE gradient evaluation (right solve, left solve, neighbour tensors, G, probes): qmps_kernel_time
   c->dominant = c->D == 16 ? "overlap_mfma_d16_kernel + adjoint + neighbour probes" : "overlap solve + adjoint + neighbour probes";
-  c->timed = !c->capturing && c->timing_period > 0 && c->launches % c->timing_period == 0;
-  const int tslot = (int)(c->samples % qmps_ctx::kRing);
-  if (c->timed) HIP_TRY(hipEventRecord(c->kev0[tslot], c->stream));
+  KernelTimer timer(c, periodic_timing(c));
+  HIP_TRY(timer.start());
   if (beside && c->fork_after_copy) {        // (the parameter upload took another path: it did not record the fork)
     c->fork_after_copy = nullptr;
     return fail(QMPS_ERR_STATE, "qmps_overlap_gradient: the parameter upload did not record the fork event");
@@ -544,7 +540,7 @@ int qmps_overlap_gradient(qmps_ctx* c, int64_t T, int kind, int n_params, const 
   const bool lazy_krylov = gp.lazy_krylov;
   qmps::OverlapArgs &a = gp.a, &l = gp.l;
   qmps::OverlapGradArgs& g = gp.g;
-  if (c->timed) { HIP_TRY(hipEventRecord(c->kev1[tslot], c->stream)); c->samples++; }
+  HIP_TRY(timer.stop());
   c->launches++;
   // f of the iterates and of their neighbours are contiguous in d_f: one copy; statuses of both solves: one copy (pinned staging)
   // (tried: the two kernels writing pinned host mirrors themselves instead of the copy kernel - 4 352 eight-byte writes over the
@@ -580,7 +576,7 @@ int qmps_overlap_gradient(qmps_ctx* c, int64_t T, int kind, int n_params, const 
       // the timed interval of this batch ends HERE when there was a second pass (Krylov pair, G, probes): kernel time, the evolve
       // drivers' gradient_ms and kernel_share_of_wall count the fall-back too (the first read-back sits inside the interval: the
       // cost of discovering the stragglers)
-      if (c->timed) HIP_TRY(hipEventRecord(c->kev1[tslot], c->stream));
+      HIP_TRY(timer.extend());
       HIP_TRY(qmps::launch_stage_copy2(c->d_f, fall, (int64_t)(fbytes / 8), c->d_status, st, (int64_t)(sbytes / 8), c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
     }

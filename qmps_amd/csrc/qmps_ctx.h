@@ -103,7 +103,13 @@ struct qmps_ctx {
                                               //   two upload slots of kMaskSlot bytes + one for the fall-back pass of qmps_overlap_gradient
   static constexpr size_t kMaskSlot = (size_t)1 << 19;
   hipEvent_t fork_after_copy = nullptr;   // one-shot: qmps_set_states_ansatz records it between the parameter upload and the tensor build
-  int* d_queue = nullptr;      // overlap kernels: counters the workgroups draw their evaluations from (qmps_create; [0, 1] D = 16 queue kernels, [2, 8) Krylov fall-back of the overlap solves: two sets of three, [8, 13) of the D = 16 environment, [13] the work counter of env_power_d4_kernel - cleared in front of its launch)
+  // d_queue: counters the workgroups draw their evaluations from ([kQueueInts], zeroed by qmps_create).  The slots:
+  //   kOverlapQueue + which        [0, 1]   work queue of the D = 16 overlap kernels (arm_queue)
+  //   kOverlapKrylov + 3 * which   [2, 8)   Krylov fall-back of the overlap solves (arm_krylov)
+  //   kEnergyKrylov                [8, 13)  Krylov fall-back of the D = 8, 16 environment solve (qmps_energy_launch)
+  //   kPowerRowCounter             [13]     work counter of env_power_d4_kernel (cleared in front of its launch)
+  enum QueueSlot : int { kOverlapQueue = 0, kOverlapKrylov = 2, kEnergyKrylov = 8, kPowerRowCounter = 13, kQueueInts = 16 };
+  int* d_queue = nullptr;
   void* d_kry = nullptr;       // D = 8, 16: iterates handed from the power kernels to the Krylov fall-back when the caller keeps no fixed points [max_batch][D][D]
   void* d_y = nullptr;         // qmps_overlap_gradient: LEFT fixed points [max_batch][D][D] (lazy)
   int64_t grad_warm_T = 0;     // d_r / d_y hold the fixed points of this many trajectories' iterates (qmps_overlap_gradient)
@@ -140,7 +146,6 @@ struct qmps_ctx {
   int timing_period = 0;            // HIP events around the dominant kernel on every timing_period-th launch (0 = never, the default:
                                     // a pair of event records costs the stream several us; qmps_set_kernel_timing_period)
   int64_t samples = 0;              // launches timed so far (ring index)
-  bool timed = false;               // this launch is one of them
   bool no_pair = false;             // QMPS_NO_PAIR: D = 4 energy-only launches with one lane per evaluation (tuning knob)
   bool pair_in_step = true;         // QMPS_LANE_IN_STEP: one-lane energy pass inside qmps_energy_launch
   int n_cus = 256;                  // compute units of the device (set in qmps_create)
@@ -237,6 +242,28 @@ struct Restore {
   Restore(const Restore&) = delete;
   Restore& operator=(const Restore&) = delete;
 };
+
+// HIP events around the dominant kernel(s) of one launch, read back by qmps_kernel_time.  The caller decides whether the launch is
+// timed; stop() ends the interval and counts the sample, extend() moves the end of a stopped interval behind later work.
+struct KernelTimer {
+  qmps_ctx* c;
+  bool on;     // this launch is timed
+  int slot;    // its event pair in kev0 / kev1
+  KernelTimer(qmps_ctx* ctx, bool timed) : c(ctx), on(timed), slot((int)(ctx->samples % qmps_ctx::kRing)) {}
+  hipError_t start() const { return on ? hipEventRecord(c->kev0[slot], c->stream) : hipSuccess; }
+  hipError_t extend() const { return on ? hipEventRecord(c->kev1[slot], c->stream) : hipSuccess; }
+  hipError_t stop() { const hipError_t e = extend(); if (on && e == hipSuccess) c->samples++; return e; }
+};
+// energy and overlap launches: every timing_period-th launch outside a graph capture (qmps_set_kernel_timing_period)
+inline bool periodic_timing(const qmps_ctx* c) { return !c->capturing && c->timing_period > 0 && c->launches % c->timing_period == 0; }
+
+// D = 8, 16: the power kernel hands an evaluation to the Krylov fall-back once its residual history predicts more than this many
+// further steps (include/qmps_hip.h "fixed-point solvers"; QMPS_KRYLOV_AFTER: tuning knob, <= 0 never hands over)
+constexpr int kKrylovAfter = 256;
+inline int krylov_after() {
+  const char* e = tuning_knob("QMPS_KRYLOV_AFTER");
+  return e ? atoi(e) : kKrylovAfter;
+}
 
 int bind(qmps_ctx* c);
 inline size_t tensor_bytes(const qmps_ctx* c) { return (size_t)32 * c->D * c->D; }
