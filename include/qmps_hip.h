@@ -39,7 +39,7 @@ extern "C" {
 #endif
 
 #define QMPS_ABI_VERSION 6
-#define QMPS_ABI_MINOR 5
+#define QMPS_ABI_MINOR 6
 
 /* error codes */
 #define QMPS_OK 0
@@ -196,7 +196,11 @@ int qmps_abi_version(void);
  *      squarings without a rank-one power: eta = the common modulus (real), QMPS_STATUS_TIED; they returned status 1 - or, with max_rounds > 50, where
  *      rounding noise breaks the tie, the quotient of a noise-picked direction with status 0 (|eta| = 1.0008, 0.54 at points of the special grid where
  *      it is 1, 0.999).  A rank-one power later than round 44 is no longer believed.  The D = 4 device-resident driver eigen-solves the 2 P neighbours of
- *      a tied point one by one (their second-order expansion has no fixed points to expand round) and leaves it as scipy's BFGS does. */
+ *      a tied point one by one (their second-order expansion has no fixed points to expand round) and leaves it as scipy's BFGS does.
+ * 6.6: qmps_overlap_gradient at a TIED iterate (D = 4): f_out is the solve's own common modulus with QMPS_OVERLAP_TWO_SIDED_F as well (the quotient of
+ *      the two mixtures used to overwrite it), g_out is NaN (it was expanded round the mixtures), and status_out combines the two solves so that a
+ *      status that is not usable beats QMPS_STATUS_TIED (a max let TIED hide NOT_CONVERGED).  qmps_evolve_bfgs at D = 4 eigen-solves the 2 n_params
+ *      neighbours of its tied iterates one by one, as qmps_evolve_bfgs_device does. */
 int qmps_abi_minor(void);
 const char* qmps_last_error(void);
 /* Test hook for the contract above ("nothing throws across the ABI"): raises a C++ exception inside the library - kind 1
@@ -457,9 +461,12 @@ int qmps_overlap_eval_ansatz(qmps_ctx* ctx, int64_t B, int kind, int n_params, c
  * method on the adjoint map y -> sum_s C_s^+ y Bm_s) and evaluates each of the 2 n_params neighbours params_t +- h e_k by
  *     eta' = <y, T'(r)> / <y, r>       (exact to second order in h: error O(h^2) ~ 1e-12 at h = 1e-6)
  * - one application of the neighbour's map instead of a power iteration.  f_out[T] = -sqrt|eta_t| (from the solve),
- * g_out[T][n_params] = (f(+h e_k) - f(-h e_k)) / 2h, status_out[T] = worst of the two solves.  QMPS_OVERLAP_WARM: both power
- * iterations start from the fixed points the previous call left resident (same T).
- * QMPS_OVERLAP_TWO_SIDED_F: f_out comes from the two-sided quotient as well, f = -sqrt|<y, T(r)> / <y, r>| - its error is the
+ * g_out[T][n_params] = (f(+h e_k) - f(-h e_k)) / 2h, status_out[T] = worst of the two solves (a status that is not usable beats
+ * QMPS_STATUS_TIED, which beats 0).  QMPS_OVERLAP_WARM: both power iterations start from the fixed points the previous call left
+ * resident (same T).  A TIED iterate (ABI 6.6; D = 4) has no fixed points to expand round: its g_out row is NaN and f_out is the
+ * solve's common modulus, with or without QMPS_OVERLAP_TWO_SIDED_F - a caller that needs its gradient eigen-solves the 2 n_params
+ * neighbours (qmps_overlap_set_group(2 n_params + 1), qmps_overlap_set_active, qmps_overlap_eval_ansatz: what qmps_evolve_bfgs does).
+ * QMPS_OVERLAP_TWO_SIDED_F: f_out comes from the two-sided quotient (not at a TIED iterate), f = -sqrt|<y, T(r)> / <y, r>| - its error is the
  * PRODUCT of the residuals of y and r, so the two solves may stop at tol ~ 1e-8 and still deliver eta to ~1e-16 (measured at
  * D = 16: |f - f_exact| < 1e-13 at tol = 1e-8, 16 power steps fewer than tol = 1e-12); the gradient inherits the residual to
  * first order (2e-8 at tol = 1e-8; central differences with h = 1e-6 carry 2e-10 of rounding themselves, scipy's own

@@ -78,37 +78,43 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
   if (carry && warm && hinv) memcpy(Hinv.data(), hinv, TP * P * sizeof(double));
   else for (int64_t t = 0; t < T; ++t) set_identity(t);
   // objective + gradient of a batch of iterates; trajectories with a failed solve come back as NaN (tools.py / new_time_evolve.py)
-  std::vector<double> fdc, fdf;
+  std::vector<double> fdc, fdf, tief, tieg;
   std::vector<int32_t> fds;
+  std::vector<unsigned char> tied;
+  // tools.batched_fd_gradient: the 2 P + 1 central-difference candidates of every (masked) iterate eigen-solved themselves - candidate
+  // t (2 P + 1) + 0 = the iterate, + 1 + k = +h e_k, + 1 + P + k = -h e_k
+  auto fd_batch = [&](const double* Z, double* fo, double* go, const unsigned char* mask) -> int {
+    const int64_t G1 = 2 * (int64_t)P + 1;
+    fdc.resize((size_t)T * G1 * P);
+    fdf.resize((size_t)T * G1);
+    fds.resize((size_t)T * G1);
+    for (int64_t t = 0; t < T; ++t)
+      for (int64_t r = 0; r < G1; ++r)
+        for (int k = 0; k < P; ++k)
+          fdc[((size_t)t * G1 + r) * P + k] = Z[(size_t)t * P + k] + (r >= 1 && (r - 1) % P == k ? (r <= P ? h : -h) : 0.0);
+    if (int e = qmps_overlap_set_group(c, G1)) return e;
+    if (mask) { if (int e = qmps_overlap_set_active(c, T, mask)) return e; }
+    int e = qmps_overlap_eval_ansatz(c, T * G1, kind, P, fdc.data(), ladder_rounds, tol, 0, fdf.data(), fds.data());
+    (void)qmps_overlap_set_group(c, 0);
+    if (e) return e;
+    for (int64_t t = 0; t < T; ++t) {
+      const double* F = &fdf[(size_t)t * G1];
+      const int32_t* S = &fds[(size_t)t * G1];
+      fo[t] = qmps::overlap_usable(S[0]) ? F[0] : nan;
+      for (int k = 0; k < P; ++k)
+        go[(size_t)t * P + k] = (qmps::overlap_usable(S[1 + k]) && qmps::overlap_usable(S[1 + P + k])) ? (F[1 + k] - F[1 + P + k]) / (2.0 * h) : nan;
+    }
+    if (counters_out) {
+      float ms = 0.f;
+      if (qmps_kernel_time(c, 1, &ms, nullptr, 0) == QMPS_OK) grad_ms += ms;
+    }
+    return QMPS_OK;
+  };
   auto value_and_grad = [&](const double* Z, double* fo, double* go, const unsigned char* mask) -> int {
     if (!two_sided) {
-      // tools.batched_fd_gradient: candidate t (2 P + 1) + 0 = the iterate, + 1 + k = +h e_k, + 1 + P + k = -h e_k
-      const int64_t G1 = 2 * (int64_t)P + 1;
-      fdc.resize((size_t)T * G1 * P);
-      fdf.resize((size_t)T * G1);
-      fds.resize((size_t)T * G1);
-      for (int64_t t = 0; t < T; ++t)
-        for (int64_t r = 0; r < G1; ++r)
-          for (int k = 0; k < P; ++k)
-            fdc[((size_t)t * G1 + r) * P + k] = Z[(size_t)t * P + k] + (r >= 1 && (r - 1) % P == k ? (r <= P ? h : -h) : 0.0);
-      if (int e = qmps_overlap_set_group(c, G1)) return e;
-      if (mask) { if (int e = qmps_overlap_set_active(c, T, mask)) return e; }
-      int e = qmps_overlap_eval_ansatz(c, T * G1, kind, P, fdc.data(), ladder_rounds, tol, 0, fdf.data(), fds.data());
-      (void)qmps_overlap_set_group(c, 0);
-      if (e) return e;
-      for (int64_t t = 0; t < T; ++t) {
-        const double* F = &fdf[(size_t)t * G1];
-        const int32_t* S = &fds[(size_t)t * G1];
-        fo[t] = qmps::overlap_usable(S[0]) ? F[0] : nan;
-        for (int k = 0; k < P; ++k)
-          go[(size_t)t * P + k] = (qmps::overlap_usable(S[1 + k]) && qmps::overlap_usable(S[1 + P + k])) ? (F[1 + k] - F[1 + P + k]) / (2.0 * h) : nan;
-      }
+      if (int e = fd_batch(Z, fo, go, mask)) return e;
       n_grad += 1.0;
       nfev += (double)T * (2 * P + 1);
-      if (counters_out) {
-        float ms = 0.f;
-        if (qmps_kernel_time(c, 1, &ms, nullptr, 0) == QMPS_OK) grad_ms += ms;
-      }
       return QMPS_OK;
     }
     if (mask) { if (int e = qmps_overlap_set_active(c, T, mask)) return e; }
@@ -120,17 +126,31 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
     }
     if (int e = qmps_overlap_gradient(c, T, kind, P, Z, h, grad_rounds, grad_tol, (warm ? QMPS_OVERLAP_WARM : 0) | QMPS_OVERLAP_TWO_SIDED_F, fo, go, st.data())) return e;
     warm = true;
+    n_grad += 1.0;
+    nfev += (double)T * (2 * P + 1);           // (scipy's count: the neighbour solves of a tie below are the same evaluation)
+    if (counters_out) {
+      float ms = 0.f;
+      if (qmps_kernel_time(c, 1, &ms, nullptr, 0) == QMPS_OK) grad_ms += ms;
+    }
+    // TIED iterates (D = 4: a non-injective state on the special grid) have an objective but no fixed points, and qmps_overlap_gradient no
+    // gradient for them: their 2 P neighbours are eigen-solved one by one, as qmps_evolve_bfgs_device does (solve_tied_neighbour) - one more
+    // batch, masked to them, only when there is a tie.  (A launch that keeps no fixed points leaves the resident ones to the next QMPS_OVERLAP_WARM.)
+    tied.assign(T, 0);
+    bool any = false;
+    for (int64_t t = 0; t < T; ++t)
+      if ((mask == nullptr || mask[t]) && st[t] == qmps::QMPS_ST_TIED) tied[t] = 1, any = true;
+    if (any) {
+      tief.resize(T);
+      tieg.resize(TP);
+      if (int e = fd_batch(Z, tief.data(), tieg.data(), tied.data())) return e;
+      for (int64_t t = 0; t < T; ++t)
+        if (tied[t]) memcpy(go + (size_t)t * P, &tieg[(size_t)t * P], (size_t)P * sizeof(double));
+    }
     for (int64_t t = 0; t < T; ++t)
       if (!qmps::overlap_usable(st[t])) {
         fo[t] = nan;
         for (int k = 0; k < P; ++k) go[(size_t)t * P + k] = nan;
       }
-    n_grad += 1.0;
-    nfev += (double)T * (2 * P + 1);
-    if (counters_out) {
-      float ms = 0.f;
-      if (qmps_kernel_time(c, 1, &ms, nullptr, 0) == QMPS_OK) grad_ms += ms;
-    }
     return QMPS_OK;
   };
   auto gmax_at_least = [&](const double* gt, double bound) {       // np.abs(g).max() >= bound, NaN-propagating: false with any NaN

@@ -583,9 +583,24 @@ int qmps_overlap_gradient(qmps_ctx* c, int64_t T, int kind, int n_params, const 
   }
   memcpy(f_out, fall, (size_t)T * sizeof(double));
   const double* fn = fall + T;
+  bool tied = false;
   for (int64_t t = 0; t < T; ++t) {
-    for (int k = 0; k < P; ++k) g_out[t * P + k] = (fn[(size_t)t * 2 * P + k] - fn[(size_t)t * 2 * P + P + k]) / (2.0 * h);
-    if (status_out) status_out[t] = st[t] > st[T + t] ? st[t] : st[T + t];
+    const int s = qmps::overlap_worse(st[t], st[T + t]);
+    if (status_out) status_out[t] = s;
+    // a TIED iterate (D = 4) has no fixed points: nothing to expand its neighbours round - no gradient (the callers eigen-solve them)
+    if (s == qmps::QMPS_ST_TIED) tied = true;
+    for (int k = 0; k < P; ++k)
+      g_out[t * P + k] = s == qmps::QMPS_ST_TIED ? __builtin_nan("") : (fn[(size_t)t * 2 * P + k] - fn[(size_t)t * 2 * P + P + k]) / (2.0 * h);
+  }
+  if (tied && (flags & QMPS_OVERLAP_TWO_SIDED_F)) {
+    // ... nor a two-sided quotient: its objective is the solve's own common modulus, which the quotient of the two mixtures overwrote in
+    // d_f - back from the right solve's eta as overlap_store computes it (a batch without a tie never gets here)
+    std::vector<double> eta((size_t)2 * T);
+    HIP_TRY(hipMemcpyAsync(eta.data(), c->d_eta, (size_t)T * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int64_t t = 0; t < T; ++t)
+      if (qmps::overlap_worse(st[t], st[T + t]) == qmps::QMPS_ST_TIED)
+        f_out[t] = -__builtin_sqrt(__builtin_sqrt(eta[2 * t] * eta[2 * t] + eta[2 * t + 1] * eta[2 * t + 1]));
   }
   c->window = 0;
   c->have_env = false; c->have_guess = false; c->have_overlap_x = false; c->acc_pending = false; c->partials_B = -1;

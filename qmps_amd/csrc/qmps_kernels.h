@@ -10,6 +10,12 @@ enum { QMPS_ST_OK = 0, QMPS_ST_NOT_CONVERGED = 1, QMPS_ST_NOT_PD = 2,
        QMPS_ST_TIED = 4 /* overlap path, D = 2, 4: dominant eigenvalues tied in modulus - eta is their common modulus, the vector is NOT a fixed point */ };
 // an overlap evaluation whose eta (hence the objective -sqrt|eta|) may be used: converged, or the common modulus of a tie (QMPS_STATUS_TIED)
 __host__ __device__ inline bool overlap_usable(int status) { return status == QMPS_ST_OK || status == QMPS_ST_TIED; }
+// the status of a pair of solves (right and left fixed point of one iterate): any status that is not usable beats TIED, TIED beats OK
+// (a plain max would let TIED = 4 hide NOT_CONVERGED = 1)
+__host__ __device__ inline int overlap_worse(int a, int b) {
+  if (!overlap_usable(a) || !overlap_usable(b)) return overlap_usable(a) ? b : (overlap_usable(b) ? a : (a > b ? a : b));
+  return a == QMPS_ST_TIED || b == QMPS_ST_TIED ? QMPS_ST_TIED : QMPS_ST_OK;
+}
 
 // Kernel arguments of the energy kernels (zero-initialise, then fill) (all pointers are HBM addresses).
 struct LaneArgs {

@@ -110,6 +110,15 @@ class _GroupedObjective:
         self.grad_warm = True
         if self.kernel_ms is not None:
             self.kernel_ms.append(self.eng.kernel_time(1)[0])
+        tied = st == L.STATUS_TIED
+        if tied.any():
+            # a TIED iterate (D = 4: a non-injective state on the special grid) has an objective but no fixed points: its gradient row is NaN
+            # and its 2 P neighbours are eigen-solved one by one (as qmps_evolve_bfgs does) - the full batch of central-difference candidates,
+            # masked to the tied trajectories (the candidates are matched to their references by group)
+            from .tools import batched_fd_gradient
+            self.eng.overlap_set_active(tied)
+            _, g_tied = batched_fd_gradient(self, X, h)
+            g = np.where(tied[:, None], g_tied, g)
         bad = ~L.overlap_usable(st)
         return np.where(bad, np.nan, f), np.where(bad[:, None], np.nan, g)
 

@@ -1027,18 +1027,56 @@ def test_device_drivers_on_the_special_grid_against_gelfand(D, engine_factory):
             assert worst < 1e-9, (D, dt, kind, P, worst)
 
 
-def test_d4_device_driver_leaves_a_tied_start_as_scipy_does(engine_factory):
+def _tied_starts_on_a_host_driver(driver, kind, grid, WW, engine_factory):
+    """The host drivers' half of the test below: the host C driver (qmps_evolve_bfgs, 'host') and the numpy lock-step loop (LockstepEvolver
+    native=False, 'numpy') report the lock-step iteration count, not one per trajectory: it is held to the slowest trajectory's scipy count, and
+    the stationary start is run on its own as well."""
+    from scipy.optimize import minimize
+
+    def run(X0):
+        if driver == 'host':
+            r = engine_factory(4, 4096).evolve_bfgs(kind, X0, WW, n_steps=1, maxiter=30, tol=1e-13)
+            return r['params_hist'][0], r['fun_start'][0], r['fun'][0], int(r['nit'][0])
+        ev = NT.LockstepEvolver(4, len(X0), X0.shape[1], None, None, 1e-13, maxiter=30, native=False, speculative=True)
+        try:
+            r = ev.step(X0, WW)
+        finally:
+            ev.close()
+        return r['x'], r['history'][0], r['fun'], int(r['nit'])
+    x, f_start, f_end, nit = run(grid)
+    sp_nit = []
+    for t, x0 in enumerate(grid):
+        A = ER.tensor(kind, 4, x0)
+        f = lambda x: ER.objective_gelfand(kind, 4, A, x, WW)
+        assert abs(f_start[t] - f(x0)) < 1e-12 and abs(f_end[t] - f(x[t])) < 1e-12, (driver, t, f_start[t], f(x0), f_end[t], f(x[t]))
+        sp = minimize(f, x0, method='BFGS', options={'maxiter': 30})
+        if t < 4:
+            assert f_end[t] < f_start[t] - 1e-4 and abs(f_end[t] - sp.fun) < 1e-7, (driver, t, f_start[t], f_end[t], sp.fun)
+            sp_nit.append(sp.nit)
+        else:
+            assert sp.nit == 0 and np.array_equal(x[t], x0) and abs(f_end[t] - sp.fun) < 1e-12, (driver, x[t], f_end[t], sp.fun)
+    assert nit >= 5 and abs(nit - max(sp_nit)) <= 4, (driver, nit, sp_nit)
+    x, _, _, nit = run(grid[4:])
+    assert nit == 0 and np.array_equal(x[0], grid[4]), (driver, nit, x)
+
+
+@pytest.mark.parametrize('driver', ['device', 'host', 'numpy'])
+def test_d4_device_driver_leaves_a_tied_start_as_scipy_does(driver, engine_factory):
     """ABI 6.5: a D = 4 trajectory STARTED at a non-injective state of the special grid (the map carries 1, 1, -1, -1: QMPS_STATUS_TIED) has an objective -
     the tie's common modulus - but no fixed points for the second-order expansion of its 2 P neighbours: those are eigen-solved one by one
     (solve_tied_neighbour, qmps_evolve_d4.hip), which is what the reference's finite differences over ARPACK see.  From four such starts the device
     reaches the minimum scipy's BFGS reaches on the same objective (Gelfand's formula on the CPU: tests/evolve_replay.objective_gelfand) in about as
-    many iterations; a tied point that is stationary (the fifth) stays, as scipy stays."""
+    many iterations; a tied point that is stationary (the fifth) stays, as scipy stays.  The same starts through the host C driver and the numpy
+    lock-step loop ('host', 'numpy'), which eigen-solve the neighbours of a tied iterate on the host's side of qmps_overlap_gradient."""
     from scipy.optimize import minimize
     grid = np.array([[2, -4, 0, 4], [2, 4, 0, -2], [-2, -4, 0, 2], [-4, 0, 2, 2], [4, 2, -4, 2]]) * (np.pi / 4)
     kind = L.ANSATZ_SHALLOW_CNOT
     eng = engine_factory(4, 4096)
     for dt in (0.05, 0.3):
         WW = WW_of(dt)
+        if driver != 'device':
+            _tied_starts_on_a_host_driver(driver, kind, grid, WW, engine_factory)
+            continue
         res = eng.evolve_bfgs_device(kind, grid, WW, n_steps=1, maxiter=30, tol=1e-13)
         assert res['failed_evaluations'] == 0
         for t, x0 in enumerate(grid):
