@@ -400,8 +400,8 @@ struct DirectD4 {
       }
     // LDL^H (replicated in the four lanes)
     P pd = O::gt0(rre[0][0]);
+    V lre[4][4], lim[4][4], d[4];
     {
-      V lre[4][4], lim[4][4], d[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         V dj = rre[j][j];
@@ -428,50 +428,94 @@ struct DirectD4 {
     }
     V bre[4][4], bim[4][4];
     b_rows(o, bre, bim);
-    // Y_tau = (row q of B_tau) r
-    V yre[4][4], yim[4][4];
+    // r = L D L^H:  rho[tau][sigma] = sum_k d_k G_tau[k] conj(G_sigma[k]) with G_tau = (row q of B_tau) L.  L is unit lower
+    // triangular, so G costs 96 multiply-adds where Y_tau = B_tau r (below) costs 224.
 #pragma unroll
     for (int tau = 0; tau < 4; ++tau)
 #pragma unroll
-      for (int l = 0; l < 4; ++l) {
-        V cr = O::splat(0.0), ci = O::splat(0.0);
+      for (int k = 0; k < 4; ++k) {
+        V cr = bre[tau][k], ci = bim[tau][k];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          // r[k][l]: k <= l stored; k > l the conjugate of r[l][k]
-          const V rr = k <= l ? rre[k][l] : rre[l][k];
-          cr = O::fma(bre[tau][k], rr, cr);
-          ci = O::fma(bim[tau][k], rr, ci);
-          if (k != l) {
-            const V ri = k < l ? rim[k][l] : -rim[l][k];
-            cr = O::fma(-bim[tau][k], ri, cr);
-            ci = O::fma(bre[tau][k], ri, ci);
-          }
+        for (int i = k + 1; i < 4; ++i) {
+          cr = O::fma(bre[tau][i], lre[i][k], cr);
+          cr = O::fma(-bim[tau][i], lim[i][k], cr);
+          ci = O::fma(bre[tau][i], lim[i][k], ci);
+          ci = O::fma(bim[tau][i], lre[i][k], ci);
         }
-        yre[tau][l] = cr;
-        yim[tau][l] = ci;
+        bre[tau][k] = cr;      // (column k reads B[i], i > k: not overwritten yet)
+        bim[tau][k] = ci;
       }
-    // rho[tau][sigma] += sum_l Y_tau[l] conj(B_sigma[l])
 #pragma unroll
-    for (int tau = 0; tau < 4; ++tau)
+    for (int tau = 0; tau < 4; ++tau) {
+      V gre[4], gim[4];
 #pragma unroll
-      for (int sg = tau; sg < 4; ++sg) {
-        V cr = yre[tau][0] * bre[sg][0], ci = O::splat(0.0);
-        cr = O::fma(yim[tau][0], bim[sg][0], cr);
+      for (int k = 0; k < 4; ++k) {
+        gre[k] = bre[tau][k] * d[k];
+        gim[k] = bim[tau][k] * d[k];
+      }
+      rho_row(tau, gre, gim, bre, bim, pre, pim);
+    }
+    // An r that fails the test is not what its factors give back (a pivot <= 0 was replaced by 1 above).  Those evaluations
+    // take rho from Y_tau = (row q of B_tau) r instead: a rare branch, uniform over the wave on the device, in which every
+    // evaluation keeps the route of its own test - no result depends on its wave-mates.
+    QMPS_SCHED_FENCE();
+    if (O::any(O::p_not(pd))) {
+      b_rows(o, bre, bim);
+#pragma unroll
+      for (int tau = 0; tau < 4; ++tau) {
+        V yre[4], yim[4];
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
-          if (l > 0) {
-            cr = O::fma(yre[tau][l], bre[sg][l], cr);
-            cr = O::fma(yim[tau][l], bim[sg][l], cr);
+          V cr = O::splat(0.0), ci = O::splat(0.0);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            // r[k][l]: k <= l stored; k > l the conjugate of r[l][k]
+            const V rr = k <= l ? rre[k][l] : rre[l][k];
+            cr = O::fma(bre[tau][k], rr, cr);
+            ci = O::fma(bim[tau][k], rr, ci);
+            if (k != l) {
+              const V ri = k < l ? rim[k][l] : -rim[l][k];
+              cr = O::fma(-bim[tau][k], ri, cr);
+              ci = O::fma(bre[tau][k], ri, ci);
+            }
           }
-          if (sg != tau) {
-            ci = O::fma(yim[tau][l], bre[sg][l], ci);
-            ci = O::fma(-yre[tau][l], bim[sg][l], ci);
-          }
+          yre[l] = cr;
+          yim[l] = ci;
         }
-        pre[tau][sg] = cr;
-        pim[tau][sg] = ci;
+        V qre[4][4], qim[4][4];
+        rho_row(tau, yre, yim, bre, bim, qre, qim);
+#pragma unroll
+        for (int sg = tau; sg < 4; ++sg) {
+          pre[tau][sg] = O::sel(pd, pre[tau][sg], qre[tau][sg]);
+          pim[tau][sg] = O::sel(pd, pim[tau][sg], qim[tau][sg]);
+        }
       }
+      QMPS_SCHED_FENCE();
+    }
     return pd;
+  }
+
+  // rho[tau][sigma] += sum_l Y[l] conj(B_sigma[l]), sigma >= tau: the lane's share of row tau of rho
+  static QMPS_CORE_FN void rho_row(int tau, const V (&yre)[4], const V (&yim)[4], const V (&bre)[4][4], const V (&bim)[4][4],
+                                   V (&pre)[4][4], V (&pim)[4][4]) {
+#pragma unroll
+    for (int sg = tau; sg < 4; ++sg) {
+      V cr = yre[0] * bre[sg][0], ci = O::splat(0.0);
+      cr = O::fma(yim[0], bim[sg][0], cr);
+#pragma unroll
+      for (int l = 0; l < 4; ++l) {
+        if (l > 0) {
+          cr = O::fma(yre[l], bre[sg][l], cr);
+          cr = O::fma(yim[l], bim[sg][l], cr);
+        }
+        if (sg != tau) {
+          ci = O::fma(yim[l], bre[sg][l], ci);
+          ci = O::fma(-yre[l], bim[sg][l], ci);
+        }
+      }
+      pre[tau][sg] = cr;
+      pim[tau][sg] = ci;
+    }
   }
 
   // E = Re sum_{s,t} h[s][t] rho[t][s] from the upper triangle of rho; h: 16 complex numbers (re, im interleaved),
