@@ -153,15 +153,6 @@ extern "C" {
  *                         D = 16: cold starts only - warm-started batches run the lean loop)
  *   QMPS_D16_ONE_WAVE     D = 16 overlap objective, batches above 2 048 candidates: one wave per candidate with a static stride
  *                         (round 2) instead of four waves per candidate drawn from a work queue (no Krylov fall-back)
- *   QMPS_NEIGHBOURS_BESIDE  D = 16 gradient batches (ShallowCNOT families): the 2 P central-difference neighbours' tensors built by a kernel
- *                         of their own on a second stream beside the eigen-solves (round 4: two cross-stream dependencies per batch) instead
- *                         of by the surplus workgroups of the eigen-solve launch itself (same tensors to rounding: the one-lane-per-column
- *                         and the wave-distributed circuit round differently)
- *   QMPS_FUSED_PROBE      ... built inside the probe kernel, never written to HBM (measured slower: the probe kernel becomes
- *                         instruction-bound, 43 us instead of 19 for 4 352 probes; kept as the third implementation of the same numbers)
- *   QMPS_EVOLVE_SPECULATIVE_HEAD  qmps_evolve_bfgs at D = 8, 16: the head of a time step (references, first gradient batch) is enqueued behind the
- *                         previous step's chain, masked by a device-side 'finished' word, instead of after the host has read back that the
- *                         previous step finished (same numbers; measured no gain: the host is back before the device runs dry)
  *   QMPS_EVOLVE_HOST_ALGEBRA  qmps_evolve_bfgs at D = 8, 16: directions, Armijo tests, H^-1 updates and masks on the HOST between two
  *                         gradient evaluations (the round-4 loop: a synchronisation and two staged copies per evaluation) instead of
  *                         in kernels on device-resident state with the host enqueueing chains of iterations.  Same numbers, bit for bit.

@@ -12,39 +12,286 @@
 using namespace qmps_host;
 
 namespace {
-// One lock-step group of qmps_evolve_bfgs: T trajectories on context c.  The histories are rows of T_hist trajectories, this
-// group's at column t_off (params / hinv already point at the group's rows).  May throw (std::vector): the callers catch.
-int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int kind, int n_params, double* params, const double* WW, int n_steps, int maxiter,
-                      double gtol, double h, double c1, int n_alphas, const double* alphas, int flags, int max_rounds, double tol,
-                      double* hinv, double* params_hist, double* f_hist, int32_t* nit_out, double* counters_out) {
-  if (int rc = bind(c)) return rc;
-  DisarmOneShots disarm{c};      // nothing armed by this driver outlives it, whichever way it ends
-  if (!params || !WW || !f_hist || !alphas) return fail(QMPS_ERR_ARG, "null argument");
-  if (flags & ~(QMPS_BFGS_CARRY_HESSIAN | QMPS_BFGS_WARM | QMPS_BFGS_TIGHT_GRADIENT | QMPS_BFGS_ADAPTIVE_GRADIENT | QMPS_BFGS_TIME_STEPS)) return fail(QMPS_ERR_ARG, "unknown flag bits 0x%x", flags);
-  const int P = n_params, NA = n_alphas;
-  if (NA < 1 || NA > 64) return fail(QMPS_ERR_ARG, "n_alphas outside [1, 64]");
-  const int64_t G = NA - 1;
-  if (T < 1 || T * (1 + 2 * (int64_t)P) > c->max_batch || T * G > c->max_batch)
-    return fail(QMPS_ERR_ARG, "T max(2 n_params + 1, n_alphas - 1) = %lld evaluations exceed max_batch = %lld",
-                (long long)(T * ((1 + 2 * (int64_t)P) > G ? (1 + 2 * (int64_t)P) : G)), (long long)c->max_batch);
-  if (n_steps < 1 || maxiter < 0 || !(gtol > 0.0) || !(h > 0.0)) return fail(QMPS_ERR_ARG, "bad n_steps / maxiter / gtol / h");
-  if (int rc = check_ansatz(c, kind, P)) return rc;
-  const bool carry = (flags & QMPS_BFGS_CARRY_HESSIAN) != 0;
-  bool warm = (flags & QMPS_BFGS_WARM) != 0;
-  const bool two_sided = c->D >= 4;       // D = 2: the 2 P + 1 central-difference candidates are eigen-solved themselves (a lane each)
-  if (warm && two_sided && c->grad_warm_T != T) return fail(QMPS_ERR_STATE, "QMPS_BFGS_WARM: the resident fixed points belong to %lld trajectories, not %lld", (long long)c->grad_warm_T, (long long)T);
-  const bool squaring = overlap_squares(c);
-  const int ladder_rounds = squaring ? (max_rounds > 60 ? 60 : max_rounds) : max_rounds;
-  const int grad_rounds = max_rounds > 100000 ? max_rounds : 100000;       // (as _GroupedObjective.value_and_grad)
-  // objective by the two-sided quotient (error ~ residual^2): the gradient batches' solves stop at 1e-8 (see qmps_hip.h)
-  double grad_tol = (flags & QMPS_BFGS_TIGHT_GRADIENT) ? tol : (tol > 1e-8 ? tol : 1e-8);
-  if (const char* e = tuning_knob("QMPS_GRAD_TOL")) grad_tol = atof(e);      // (tuning builds: profiles/EXPERIMENTS.md round 5)
-  // QMPS_BFGS_ADAPTIVE_GRADIENT (D = 8, 16): the solves of a trajectory's gradient stop at clamp(1e-3 max|g|, grad_tol, 1e-6), g the
-  // trajectory's current gradient (first evaluation of a time step: the gradient the previous step's first evaluation found; first
-  // step of a call: grad_tol).  The objective still comes from the two-sided quotient (error ~ residual^2 <= 1e-12, far inside the
-  // Armijo margin c1 |slope|: 1e-6 |g|^2 against 1e-4 |g|^2); the gradient carries a relative error <= ~1e-3.
-  const bool adaptive = (flags & QMPS_BFGS_ADAPTIVE_GRADIENT) != 0 && (flags & QMPS_BFGS_TIGHT_GRADIENT) == 0 && two_sided && (c->D == 8 || c->D == 16);
-  const double tol_min = grad_tol, tol_max = grad_tol > 1e-6 ? grad_tol : 1e-6, tol_rel = 1e-3;
+// The inputs and outputs of one lock-step group of qmps_evolve_bfgs: T trajectories on context c.  The histories are rows of T_hist
+// trajectories, this group's at column t_off; params, hinv, nit_out and counters_out point at the group's own rows.
+struct BfgsGroup {
+  qmps_ctx* c;
+  int64_t T, T_hist, t_off;
+  int kind, P;
+  double* params;
+  const double* WW;
+  int n_steps, maxiter;
+  double gtol, h, c1;
+  int NA;
+  const double* alphas;
+  int flags, max_rounds;
+  double tol;
+  double* hinv;
+  double* params_hist;
+  double* f_hist;
+  int32_t* nit_out;
+  double* counters_out;
+};
+
+// What the shared front derives from a group's call, and what either path leaves for the shared write-back.
+struct BfgsRun {
+  bool carry, warm, two_sided, adaptive;      // warm: the resident fixed points start the next gradient's solves (set by the first one)
+  int ladder_rounds, grad_rounds;
+  double grad_tol, tol_min, tol_max, tol_rel;
+  int64_t G;                          // rungs of the ladder behind the full step
+  size_t TP;
+  std::vector<double> X, Hinv;        // the iterates and their inverse Hessians
+  double n_grad = 0.0, n_ladder = 0.0, nfev = 0.0, grad_ms = 0.0;      // counters_out
+};
+
+void set_identity(std::vector<double>& Hinv, int64_t t, int P) {
+  double* Ht = &Hinv[(size_t)t * P * P];
+  for (int a = 0; a < P; ++a)
+    for (int b = 0; b < P; ++b) Ht[a * P + b] = a == b ? 1.0 : 0.0;
+}
+
+// ---- D = 8, 16: the algebra between two evaluations on the device (qmps_evolve_lockstep.hip) -------------------------------
+// x, g, H^-1, f, the masks and a control word live in HBM; the host enqueues [direction -> evaluation -> accept] chains and reads
+// the control word back once per chain.  The iteration in which a trajectory rejects the full step is finished on the device as
+// well: its ladder, the gradient at the accepted points and the update are enqueued behind the chain (enqueue_ladder, step kernel
+// mode 3) - the host loop's arithmetic, the same decisions.
+int evolve_bfgs_device_algebra(const BfgsGroup& job, BfgsRun& run) {
+  qmps_ctx* c = job.c;
+  const int64_t T = job.T, G = run.G;
+  const int kind = job.kind, P = job.P, NA = job.NA, n_steps = job.n_steps, maxiter = job.maxiter;
+  const double h = job.h, tol = job.tol;
+  const size_t TP = run.TP;
+  const bool adaptive = run.adaptive;
+  bool& warm = run.warm;
+  double &n_grad = run.n_grad, &n_ladder = run.n_ladder, &nfev = run.nfev, &grad_ms = run.grad_ms;
+  int rc = QMPS_OK;
+  struct {
+    double *X, *G, *H, *F, *Dv, *slope, *Xc, *fh, *ph, *F0, *asel, *alphas, *cand, *tolarr, *g0max;
+    int* ctl;          // [0, 4) the control word; [16, 16 + maxiter + 1): trajectories that rejected the full step, per iteration of the time step
+    unsigned char *active, *eff, *need;
+  } dv = {};
+  // first chain of a time step: as many iterations as the previous step took (the lock-step count is steady along an evolution with
+  // carried Hessians; an idle iteration at the tail of a chain costs ~40 us of empty launches, a chain too short a synchronisation
+  // per further iteration); QMPS_EVOLVE_CHAIN (tuning builds) fixes it
+  int chain_fixed = 0, nit_prev = 4;
+  std::vector<unsigned char> rej_prev;      // iterations of the previous time step in which a full step was rejected
+  if (const char* e = tuning_knob("QMPS_EVOLVE_CHAIN")) chain_fixed = atoi(e) > 0 ? atoi(e) : 0;
+  {
+    const size_t n_ctl = 16 + 2 * ((size_t)maxiter + 2);
+    const size_t n_dbl = 4 * TP + TP * P + 6 * (size_t)T + (size_t)n_steps * 2 * T + (size_t)n_steps * TP + (size_t)NA + (size_t)T * (G > 0 ? G : 1) * P;
+    const size_t bytes = n_dbl * sizeof(double) + (n_ctl + (n_ctl & 1)) * sizeof(int) + 3 * (((size_t)T + 7) / 8 * 8) + 64;
+    if (bytes > c->d_lock_bytes) {
+      if (c->d_lock) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_lock)); }
+      c->d_lock = nullptr; c->d_lock_bytes = 0;
+      HIP_TRY(hipMalloc(&c->d_lock, bytes));
+      c->d_lock_bytes = bytes;
+    }
+    double* q = (double*)c->d_lock;
+    dv.X = q; q += TP; dv.G = q; q += TP; dv.Dv = q; q += TP; dv.Xc = q; q += TP;
+    dv.H = q; q += TP * P; dv.F = q; q += T; dv.slope = q; q += T; dv.F0 = q; q += T; dv.asel = q; q += T; dv.tolarr = q; q += T; dv.g0max = q; q += T;
+    dv.fh = q; q += (size_t)n_steps * 2 * T; dv.ph = q; q += (size_t)n_steps * TP; dv.alphas = q; q += NA; dv.cand = q; q += (size_t)T * (G > 0 ? G : 1) * P;
+    dv.ctl = (int*)q;
+    dv.active = (unsigned char*)(dv.ctl + n_ctl + (n_ctl & 1)); dv.eff = dv.active + ((size_t)T + 7) / 8 * 8; dv.need = dv.eff + ((size_t)T + 7) / 8 * 8;
+    if (!c->d_active) HIP_TRY(hipMalloc((void**)&c->d_active, ((size_t)c->max_batch + 7) / 8 * 8));
+    if (!c->h_ctl) HIP_TRY(hipHostMalloc((void**)&c->h_ctl, 4096, hipHostMallocDefault));
+    if ((rc = ensure_overlap_outputs(c))) return rc;
+    if (!c->d_y) HIP_TRY(hipMalloc(&c->d_y, (size_t)c->max_batch * env_bytes(c)));
+    { const size_t nD = (size_t)c->D * c->D; if ((rc = ensure_scratch(c, (size_t)T * (4 * nD + 1) * 16 + 256))) return rc; }
+    if ((rc = ensure_refs(c, T))) return rc;
+    if (!c->aux_stream) {
+      HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
+      HIP_TRY(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
+    }
+    const std::vector<double> tol0(adaptive ? T : 0, run.tol_min);      // (first evaluation: the tightest)
+    HIP_TRY(hipMemcpyAsync(dv.X, run.X.data(), TP * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dv.H, run.Hinv.data(), TP * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dv.alphas, job.alphas, (size_t)NA * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(dv.ctl, 0, 16 * sizeof(int), c->stream));      // control word, barrier accumulators and arrival counter
+    if (adaptive) {
+      HIP_TRY(hipMemcpyAsync(dv.tolarr, tol0.data(), (size_t)T * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemsetAsync(dv.g0max, 0, (size_t)T * sizeof(double), c->stream));
+    }
+    if ((rc = set_ww(c, job.WW))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));       // (X, Hinv, tol0 are pageable host vectors)
+    c->window = 0;
+    forget_resident_state(c);
+    c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0; c->tensors_valid = false; c->n_states = 0;
+  }
+  const bool beside = neighbour_build(c, T, kind, P) == NeighbourBuild::Beside;
+  auto lock_args = [&](int step, bool reset_h, int mode) {
+    qmps::LockstepArgs la;
+    memset(&la, 0, sizeof(la));
+    la.X = dv.X; la.G = dv.G; la.H = dv.H; la.F = dv.F; la.Dv = dv.Dv; la.slope = dv.slope; la.Xc = dv.Xc;
+    la.F0 = dv.F0; la.asel = dv.asel; la.alphas = dv.alphas; la.cand = dv.cand; la.NA = NA;
+    la.tol_next = adaptive ? dv.tolarr : nullptr; la.g0max = dv.g0max; la.tol_min = run.tol_min; la.tol_max = run.tol_max; la.tol_rel = run.tol_rel;
+    la.fb = c->d_f; la.st = c->d_status; la.active = dv.active; la.eff = dv.eff; la.need = dv.need; la.ctl = dv.ctl;
+    la.fh_start = dv.fh + (size_t)step * 2 * T; la.fh_end = dv.fh + ((size_t)step * 2 + 1) * T; la.ph = dv.ph + (size_t)step * TP; la.mode = mode;
+    la.step_id = step + 1; la.hist_off = ((step + 1) & 1) * (maxiter + 2);
+    la.T = (int)T; la.P = P; la.maxiter = maxiter; la.reset_h = reset_h ? 1 : 0; la.h = h; la.gtol = job.gtol; la.c1 = job.c1; la.alpha0 = job.alphas[0];
+    return la;
+  };
+  // QMPS_BFGS_TIME_STEPS (with counters_out): no event pairs around the evaluations and no one-iteration chains - the run is the timed
+  // region's - but ONE pair per time step, from its first kernel to the last one enqueued: counters_out[3] = the milliseconds the device
+  // spent on this call's kernels (idle launches at a chain's tail included; the host's gap between two time steps not)
+  const bool time_steps = job.counters_out != nullptr && (job.flags & QMPS_BFGS_TIME_STEPS) != 0;
+  const bool per_eval = job.counters_out != nullptr && !time_steps;
+  if (time_steps && !c->step_ev0) {
+    HIP_TRY(hipEventCreate(&c->step_ev0));
+    HIP_TRY(hipEventCreate(&c->step_ev1));
+  }
+  int lock_epoch = 0;          // launches of the step kernel on this control word (its grid barrier counts arrivals against it)
+  const int lock_blocks = qmps::lockstep_step_blocks((int)T, P);
+  auto launch_step = [&](int step, bool reset_h, int mode) -> int {
+    qmps::LockstepArgs a2 = lock_args(step, reset_h, mode);
+    a2.epoch = ++lock_epoch;
+    a2.blocks = lock_blocks;
+    HIP_TRY(qmps::launch_lockstep_step(a2, c->stream));
+    return QMPS_OK;
+  };
+  // one evaluation of the rows at d_src (iterate tensors, both fixed points, neighbours, probes), enqueued only
+  auto dev_gradient = [&](const double* d_src, const unsigned char* mask) -> int {
+    HIP_TRY(qmps::launch_ansatz(c->D, kind, d_src, P, c->d_A, T, c->stream));      // (every row: a masked-out row's tensor is never read)
+    if (beside) HIP_TRY(hipEventRecord(c->aux_fork, c->stream));      // (the second stream builds the neighbours' tensors)
+    KernelTimer timer(c, per_eval);
+    HIP_TRY(timer.start());
+    c->dominant = c->D == 16 ? "overlap_mfma_d16_kernel + adjoint + neighbour probes" : "overlap solve + adjoint + neighbour probes";
+    GradPass gp;
+    if (int e = enqueue_gradient_kernels(c, T, kind, P, d_src, h, run.grad_rounds, run.grad_tol, warm, true, mask, false, gp, adaptive ? dv.tolarr : nullptr)) return e;
+    HIP_TRY(timer.stop());
+    c->launches++;
+    warm = true;
+    c->grad_warm_T = T;
+    return QMPS_OK;
+  };
+  for (int step = 0; step < n_steps && rc == QMPS_OK; ++step) {
+    const bool reset_h = !(run.carry && (step > 0 || ((job.flags & QMPS_BFGS_WARM) != 0 && job.hinv)));
+    if (time_steps) HIP_TRY(hipEventRecord(c->step_ev0, c->stream));
+    HIP_TRY(qmps::launch_ansatz(c->D, kind, dv.X, P, c->d_ref, T, c->stream));        // the step's references: A_t = tensor(current parameters)
+    c->overlap_refs = T;
+    c->overlap_group = 0;
+    if ((rc = dev_gradient(dv.X, nullptr))) break;
+    if ((rc = launch_step(step, reset_h, 1))) break;      // f, g, active set; the first direction
+    n_grad += 1.0;
+    nfev += (double)T * (2 * P + 1);
+    int nit = 0;
+    const qmps::LockstepArgs la = lock_args(step, false, 0);
+    // the ladder of an iteration that stopped on rejected full steps, and what follows it - enqueued only: candidates of every
+    // trajectory, their solves masked by `need` and started from the rejected steps' fixed points, the verdict, the gradient at the
+    // accepted points (masked alike), the update and the next direction (step kernel, mode 3).  Every kernel of it does nothing
+    // when nothing was rejected, so it may be enqueued blindly where the previous time step had a rejection.
+    auto enqueue_ladder = [&]() -> int {
+      if (G <= 0) return fail(QMPS_ERR_ARG, "a rejected full step needs a ladder (n_alphas >= 2)");
+      HIP_TRY(qmps::launch_lockstep_ladder_cand(la, c->stream));
+      HIP_TRY(hipMemcpyAsync(c->d_active, dv.need, (size_t)T, hipMemcpyDeviceToDevice, c->stream));
+      c->mask_stash_n = 0; c->mask_host = nullptr; c->active_n = T;
+      c->ans_have = true; c->ans_kind = kind; c->ans_P = P; c->ans_src = dv.cand; c->ans_i = nullptr; c->ans_nsh = 0;
+      c->tensors_valid = false; c->n_states = T * G; c->window = 0;
+      c->overlap_group = G;
+      c->warm_from_group = (c->grad_warm_T == T) ? G : 0;      // (resident: the fixed points of the rejected full steps)
+      const int e = qmps_overlap_launch(c, T * G, run.ladder_rounds, tol, 0);
+      c->overlap_group = 0;
+      c->ans_have = false; c->ans_src = nullptr; c->tensors_valid = false; c->n_states = 0;
+      if (e) return e;
+      HIP_TRY(qmps::launch_lockstep_ladder_pick(la, c->d_f, c->d_status, c->stream));
+      if (int e2 = dev_gradient(dv.Xc, dv.need)) return e2;
+      return launch_step(step, false, 3);
+    };
+    bool first_chain = true;
+    for (;;) {
+      // with counters: one iteration per chain, so that every evaluation's event pair can be read (the timed region runs without)
+      int K = per_eval ? 1 : (first_chain ? (chain_fixed > 0 ? chain_fixed : nit_prev) : 1);
+      K = K < 1 ? 1 : K;
+      K = K < maxiter - nit ? K : maxiter - nit;
+      first_chain = false;
+      for (int i = 0; i < K; ++i) {
+        if ((rc = dev_gradient(dv.Xc, dv.eff))) break;
+        if ((rc = launch_step(step, false, 0))) break;               // finish the iteration, open the next
+        // the previous time step had a rejection at this iteration: its ladder rides along (empty launches if nothing is rejected now)
+        if (!per_eval && (size_t)(nit + i) < rej_prev.size() && rej_prev[nit + i] && (rc = enqueue_ladder())) break;
+      }
+      if (rc) break;
+      if (time_steps) HIP_TRY(hipEventRecord(c->step_ev1, c->stream));
+      const size_t n_read = 16 + 2 * ((size_t)maxiter + 2);
+      HIP_TRY(hipMemcpyAsync(c->h_ctl, dv.ctl, n_read * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      const int* hist = c->h_ctl + 16 + ((step + 1) & 1) * (maxiter + 2);
+      const bool finished = c->h_ctl[5] == step + 1;
+      const int n_act = finished ? 0 : c->h_ctl[0], nit_dev = finished ? c->h_ctl[6] : c->h_ctl[2], stop = finished ? 0 : c->h_ctl[3];
+      if (per_eval && K > 0) {
+        float ms = 0.f;
+        if ((nit_dev > nit || stop) && qmps_kernel_time(c, 1, &ms, nullptr, 0) == QMPS_OK) grad_ms += ms;
+      }
+      if (per_eval) {       // (K = 1: exact counts, as the host loop's)
+        n_grad += (double)(nit_dev - nit) + (stop ? 1.0 : 0.0);
+        nfev += ((double)(nit_dev - nit) + (stop ? 1.0 : 0.0)) * (double)T * (2 * P + 1);
+      }
+      nit = nit_dev;
+      if (finished) {
+        rej_prev.assign((size_t)nit, 0);
+        for (int i = 0; i < nit; ++i) rej_prev[i] = hist[i] > 0 ? 1 : 0;
+        break;
+      }
+      if (stop) {
+        // some trajectories rejected the full step and no ladder was waiting: enqueue it now (no further synchronisation - the
+        // next chain follows at once)
+        if ((rc = enqueue_ladder())) break;
+        if (time_steps) HIP_TRY(hipEventRecord(c->step_ev1, c->stream));
+        if (per_eval) {
+          HIP_TRY(hipStreamSynchronize(c->stream));
+          float ms = 0.f;
+          if (qmps_kernel_time(c, 1, &ms, nullptr, 0) == QMPS_OK) grad_ms += ms;
+          n_ladder += 1.0;
+          n_grad += 1.0;
+          nfev += (double)T * G + (double)T * (2 * P + 1);
+        }
+        nit += 1;            // (the step kernel of mode 3 counts it on the device; the next read-back finds the step finished or not)
+        continue;
+      }
+      if (n_act == 0 || nit >= maxiter) break;
+    }
+    if (rc) break;
+    if (time_steps) {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, c->step_ev0, c->step_ev1));
+      grad_ms += ms;
+    }
+    // (the step's record - objective at the end, parameters - was written by the last live step kernel; on the device until the call ends)
+    nit_prev = nit > 0 ? nit : 1;
+    if (job.nit_out) job.nit_out[step] = nit;
+  }
+  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+  std::vector<double> fh((size_t)n_steps * 2 * T), ph(job.params_hist ? (size_t)n_steps * TP : 0);
+  HIP_TRY(hipMemcpyAsync(fh.data(), dv.fh, fh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (job.params_hist) HIP_TRY(hipMemcpyAsync(ph.data(), dv.ph, ph.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(run.X.data(), dv.X, TP * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(run.Hinv.data(), dv.H, TP * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int step = 0; step < n_steps; ++step) {
+    memcpy(job.f_hist + (size_t)step * 2 * job.T_hist + job.t_off, &fh[(size_t)step * 2 * T], (size_t)T * sizeof(double));
+    memcpy(job.f_hist + ((size_t)step * 2 + 1) * job.T_hist + job.t_off, &fh[((size_t)step * 2 + 1) * T], (size_t)T * sizeof(double));
+    if (job.params_hist) memcpy(job.params_hist + ((size_t)step * job.T_hist + job.t_off) * P, &ph[(size_t)step * TP], TP * sizeof(double));
+  }
+  c->window = 0;
+  forget_resident_state(c);
+  return QMPS_OK;
+}
+
+// ---- the host loop: the algebra between two batched evaluations on the host (the round-4 driver).  D = 2, 4, and D = 8, 16 under
+// QMPS_EVOLVE_HOST_ALGEBRA, QMPS_D16_BLOCK or QMPS_D16_ONE_WAVE (the test-suite runs it against the device algebra).
+int evolve_bfgs_host_loop(const BfgsGroup& job, BfgsRun& run) {
+  qmps_ctx* c = job.c;
+  const int64_t T = job.T, G = run.G;
+  const int kind = job.kind, P = job.P, NA = job.NA, maxiter = job.maxiter;
+  const double h = job.h, gtol = job.gtol, c1 = job.c1, tol = job.tol;
+  const double* alphas = job.alphas;
+  const size_t TP = run.TP;
+  const bool two_sided = run.two_sided, adaptive = run.adaptive;
+  const double tol_min = run.tol_min, tol_max = run.tol_max, tol_rel = run.tol_rel;
+  bool& warm = run.warm;
+  std::vector<double> &X = run.X, &Hinv = run.Hinv;
+  double &n_grad = run.n_grad, &n_ladder = run.n_ladder, &nfev = run.nfev, &grad_ms = run.grad_ms;
   std::vector<double> tolv(adaptive ? T : 0, tol_min), g0max_prev(adaptive ? T : 0, 0.0);
   auto tol_rule = [&](double m, bool isnan_) {
     const double t = tol_rel * m;
@@ -60,23 +307,10 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
     }
     return m;
   };
-  const size_t TP = (size_t)T * P;
   const double nan = __builtin_nan("");
-  std::vector<double> X(params, params + TP), Hinv(TP * P), f(T), g(TP), d(TP), slope(T), fs(T), gs(TP), fn(T), gn(TP), Xc(TP), Xn(TP), s(TP), Fc((size_t)T * NA),
-      cand, Fl, Hy(P);
+  std::vector<double> f(T), g(TP), d(TP), slope(T), fs(T), gs(TP), fn(T), gn(TP), Xc(TP), Xn(TP), s(TP), Fc((size_t)T * NA), cand, Fl, Hy(P);
   std::vector<int32_t> st(T), stl;
   std::vector<unsigned char> active(T), moved(T), need(T);
-  // (a pair of event records around a batch costs the stream ~12 us: only when asked for; restored on EVERY way out of this function)
-  Restore<int> period_guard(c->timing_period, counters_out ? 1 : 0);
-  Restore<bool> stash_guard(c->stash_masks, true);          // (every batch below ends with a synchronisation)
-  double n_grad = 0.0, n_ladder = 0.0, nfev = 0.0, grad_ms = 0.0;
-  auto set_identity = [&](int64_t t) {
-    double* Ht = &Hinv[(size_t)t * P * P];
-    for (int a = 0; a < P; ++a)
-      for (int b = 0; b < P; ++b) Ht[a * P + b] = a == b ? 1.0 : 0.0;
-  };
-  if (carry && warm && hinv) memcpy(Hinv.data(), hinv, TP * P * sizeof(double));
-  else for (int64_t t = 0; t < T; ++t) set_identity(t);
   // objective + gradient of a batch of iterates; trajectories with a failed solve come back as NaN (tools.py / new_time_evolve.py)
   std::vector<double> fdc, fdf, tief, tieg;
   std::vector<int32_t> fds;
@@ -94,7 +328,7 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
           fdc[((size_t)t * G1 + r) * P + k] = Z[(size_t)t * P + k] + (r >= 1 && (r - 1) % P == k ? (r <= P ? h : -h) : 0.0);
     if (int e = qmps_overlap_set_group(c, G1)) return e;
     if (mask) { if (int e = qmps_overlap_set_active(c, T, mask)) return e; }
-    int e = qmps_overlap_eval_ansatz(c, T * G1, kind, P, fdc.data(), ladder_rounds, tol, 0, fdf.data(), fds.data());
+    int e = qmps_overlap_eval_ansatz(c, T * G1, kind, P, fdc.data(), run.ladder_rounds, tol, 0, fdf.data(), fds.data());
     (void)qmps_overlap_set_group(c, 0);
     if (e) return e;
     for (int64_t t = 0; t < T; ++t) {
@@ -104,7 +338,7 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
       for (int k = 0; k < P; ++k)
         go[(size_t)t * P + k] = (qmps::overlap_usable(S[1 + k]) && qmps::overlap_usable(S[1 + P + k])) ? (F[1 + k] - F[1 + P + k]) / (2.0 * h) : nan;
     }
-    if (counters_out) {
+    if (job.counters_out) {
       float ms = 0.f;
       if (qmps_kernel_time(c, 1, &ms, nullptr, 0) == QMPS_OK) grad_ms += ms;
     }
@@ -124,11 +358,11 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
       HIP_TRY(hipStreamSynchronize(c->stream));
       c->grad_tol_in = c->d_tolarr;
     }
-    if (int e = qmps_overlap_gradient(c, T, kind, P, Z, h, grad_rounds, grad_tol, (warm ? QMPS_OVERLAP_WARM : 0) | QMPS_OVERLAP_TWO_SIDED_F, fo, go, st.data())) return e;
+    if (int e = qmps_overlap_gradient(c, T, kind, P, Z, h, run.grad_rounds, run.grad_tol, (warm ? QMPS_OVERLAP_WARM : 0) | QMPS_OVERLAP_TWO_SIDED_F, fo, go, st.data())) return e;
     warm = true;
     n_grad += 1.0;
     nfev += (double)T * (2 * P + 1);           // (scipy's count: the neighbour solves of a tie below are the same evaluation)
-    if (counters_out) {
+    if (job.counters_out) {
       float ms = 0.f;
       if (qmps_kernel_time(c, 1, &ms, nullptr, 0) == QMPS_OK) grad_ms += ms;
     }
@@ -163,254 +397,14 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
     return m >= bound;
   };
   int rc = QMPS_OK;
-  // ---- D = 8, 16: the algebra between two evaluations on the device (qmps_evolve_lockstep.hip) -------------------------------
-  // x, g, H^-1, f, the masks and a control word live in HBM; the host enqueues [direction -> evaluation -> accept] chains and reads
-  // the control word back once per chain.  The iteration in which a trajectory rejects the full step is finished by the host
-  // code below (ladder, gradient at the accepted point, update) on a downloaded copy of the state - the same code, the same
-  // decisions.  QMPS_EVOLVE_HOST_ALGEBRA selects the host loop for everything (the round-4 driver; the test-suite runs both).
-  const bool dev_algebra = two_sided && (c->D == 8 || c->D == 16) && P <= 32 && T <= 65535 && maxiter <= 480 && documented_switch("QMPS_EVOLVE_HOST_ALGEBRA") == nullptr &&
-                           documented_switch("QMPS_D16_BLOCK") == nullptr && documented_switch("QMPS_D16_ONE_WAVE") == nullptr;
-  struct {
-    double *X, *G, *H, *F, *Dv, *slope, *Xc, *fh, *ph, *F0, *asel, *alphas, *cand, *tolarr, *g0max;
-    int* ctl;          // [0, 4) the control word; [16, 16 + maxiter + 1): trajectories that rejected the full step, per iteration of the time step
-    unsigned char *active, *eff, *need, *head;
-  } dv = {};
-  // first chain of a time step: as many iterations as the previous step took (the lock-step count is steady along an evolution with
-  // carried Hessians; an idle iteration at the tail of a chain costs ~40 us of empty launches, a chain too short a synchronisation
-  // per further iteration); QMPS_EVOLVE_CHAIN (tuning builds) fixes it
-  int chain_fixed = 0, nit_prev = 4;
-  std::vector<unsigned char> rej_prev;      // iterations of the previous time step in which a full step was rejected
-  if (const char* e = tuning_knob("QMPS_EVOLVE_CHAIN")) chain_fixed = atoi(e) > 0 ? atoi(e) : 0;
-  if (dev_algebra) {
-    const size_t n_ctl = 16 + 2 * ((size_t)maxiter + 2);
-    const size_t n_dbl = 4 * TP + TP * P + 6 * (size_t)T + (size_t)n_steps * 2 * T + (size_t)n_steps * TP + (size_t)NA + (size_t)T * (G > 0 ? G : 1) * P;
-    const size_t bytes = n_dbl * sizeof(double) + (n_ctl + (n_ctl & 1)) * sizeof(int) + 4 * (((size_t)T + 7) / 8 * 8) + 64;
-    if (bytes > c->d_lock_bytes) {
-      if (c->d_lock) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_lock)); }
-      c->d_lock = nullptr; c->d_lock_bytes = 0;
-      HIP_TRY(hipMalloc(&c->d_lock, bytes));
-      c->d_lock_bytes = bytes;
-    }
-    double* q = (double*)c->d_lock;
-    dv.X = q; q += TP; dv.G = q; q += TP; dv.Dv = q; q += TP; dv.Xc = q; q += TP;
-    dv.H = q; q += TP * P; dv.F = q; q += T; dv.slope = q; q += T; dv.F0 = q; q += T; dv.asel = q; q += T; dv.tolarr = q; q += T; dv.g0max = q; q += T;
-    dv.fh = q; q += (size_t)n_steps * 2 * T; dv.ph = q; q += (size_t)n_steps * TP; dv.alphas = q; q += NA; dv.cand = q; q += (size_t)T * (G > 0 ? G : 1) * P;
-    dv.ctl = (int*)q;
-    dv.active = (unsigned char*)(dv.ctl + n_ctl + (n_ctl & 1)); dv.eff = dv.active + ((size_t)T + 7) / 8 * 8; dv.need = dv.eff + ((size_t)T + 7) / 8 * 8; dv.head = dv.need + ((size_t)T + 7) / 8 * 8;
-    if (!c->d_active) HIP_TRY(hipMalloc((void**)&c->d_active, ((size_t)c->max_batch + 7) / 8 * 8));
-    if (!c->h_ctl) HIP_TRY(hipHostMalloc((void**)&c->h_ctl, 4096, hipHostMallocDefault));
-    if ((rc = ensure_overlap_outputs(c))) return rc;
-    if (!c->d_y) HIP_TRY(hipMalloc(&c->d_y, (size_t)c->max_batch * env_bytes(c)));
-    { const size_t nD = (size_t)c->D * c->D; if ((rc = ensure_scratch(c, (size_t)T * (4 * nD + 1) * 16 + 256))) return rc; }
-    if ((rc = ensure_refs(c, T))) return rc;
-    if (!c->aux_stream) {
-      HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
-    }
-    HIP_TRY(hipMemcpyAsync(dv.X, X.data(), TP * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dv.H, Hinv.data(), TP * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dv.alphas, alphas, (size_t)NA * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(dv.ctl, 0, 16 * sizeof(int), c->stream));      // control word, barrier accumulators and arrival counter
-    if (adaptive) {
-      HIP_TRY(hipMemcpyAsync(dv.tolarr, tolv.data(), (size_t)T * sizeof(double), hipMemcpyHostToDevice, c->stream));      // (first evaluation: the tightest)
-      HIP_TRY(hipMemsetAsync(dv.g0max, 0, (size_t)T * sizeof(double), c->stream));
-    }
-    if ((rc = set_ww(c, WW))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));       // (X, Hinv are pageable host vectors)
-    c->window = 0;
-    c->have_env = false; c->have_guess = false; c->have_overlap_x = false; c->acc_pending = false; c->partials_B = -1;
-    c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0; c->tensors_valid = false; c->n_states = 0;
-  }
-  const bool beside_dev = T <= 1024 && !c->one_stream;
-  // (no second stream when the neighbours' tensors are built inside the pair launch or inside the probe kernel)
-  const bool fused_probe_dev = (qmps::overlap_probe_fusable(c->D, kind, P) && documented_switch("QMPS_FUSED_PROBE") != nullptr) ||
-                               (qmps::neighbour_build_in_pair(c->D, kind, P) && documented_switch("QMPS_NEIGHBOURS_BESIDE") == nullptr &&
-                                documented_switch("QMPS_D16_BLOCK") == nullptr && documented_switch("QMPS_D16_ONE_WAVE") == nullptr);
-  auto lock_args = [&](int step, bool reset_h, int mode) {
-    qmps::LockstepArgs la;
-    memset(&la, 0, sizeof(la));
-    la.X = dv.X; la.G = dv.G; la.H = dv.H; la.F = dv.F; la.Dv = dv.Dv; la.slope = dv.slope; la.Xc = dv.Xc;
-    la.F0 = dv.F0; la.asel = dv.asel; la.alphas = dv.alphas; la.cand = dv.cand; la.NA = NA;
-    la.tol_next = adaptive ? dv.tolarr : nullptr; la.g0max = dv.g0max; la.tol_min = tol_min; la.tol_max = tol_max; la.tol_rel = tol_rel;
-    la.fb = c->d_f; la.st = c->d_status; la.active = dv.active; la.eff = dv.eff; la.need = dv.need; la.ctl = dv.ctl;
-    la.fh_start = dv.fh + (size_t)step * 2 * T; la.fh_end = dv.fh + ((size_t)step * 2 + 1) * T; la.ph = dv.ph + (size_t)step * TP; la.mode = mode;
-    la.step_id = step + 1; la.head_mask = dv.head; la.hist_off = ((step + 1) & 1) * (maxiter + 2);
-    la.T = (int)T; la.P = P; la.maxiter = maxiter; la.reset_h = reset_h ? 1 : 0; la.h = h; la.gtol = gtol; la.c1 = c1; la.alpha0 = alphas[0];
-    return la;
-  };
-  // QMPS_BFGS_TIME_STEPS (with counters_out): no event pairs around the evaluations and no one-iteration chains - the run is the timed
-  // region's - but ONE pair per time step, from its first kernel to the last one enqueued: counters_out[3] = the milliseconds the device
-  // spent on this call's kernels (idle launches at a chain's tail included; the host's gap between two time steps not)
-  const bool time_steps = dev_algebra && counters_out != nullptr && (flags & QMPS_BFGS_TIME_STEPS) != 0;
-  const bool per_eval = counters_out != nullptr && !time_steps;
-  if (time_steps && !c->step_ev0) {
-    HIP_TRY(hipEventCreate(&c->step_ev0));
-    HIP_TRY(hipEventCreate(&c->step_ev1));
-  }
-  int lock_epoch = 0;          // launches of the step kernel on this control word (its grid barrier counts arrivals against it)
-  const int lock_blocks = dev_algebra ? qmps::lockstep_step_blocks((int)T, P) : 0;
-  auto launch_step = [&](int step, bool reset_h, int mode) -> int {
-    qmps::LockstepArgs a2 = lock_args(step, reset_h, mode);
-    a2.epoch = ++lock_epoch;
-    a2.blocks = lock_blocks;
-    HIP_TRY(qmps::launch_lockstep_step(a2, c->stream));
-    return QMPS_OK;
-  };
-  // one evaluation of the rows at d_src (iterate tensors, both fixed points, neighbours, probes), enqueued only
-  auto dev_gradient = [&](const double* d_src, const unsigned char* mask) -> int {
-    HIP_TRY(qmps::launch_ansatz(c->D, kind, d_src, P, c->d_A, T, c->stream));      // (every row: a masked-out row's tensor is never read)
-    if (beside_dev && !fused_probe_dev) HIP_TRY(hipEventRecord(c->aux_fork, c->stream));      // (the second stream builds the neighbours' tensors)
-    KernelTimer timer(c, per_eval);
-    HIP_TRY(timer.start());
-    c->dominant = c->D == 16 ? "overlap_mfma_d16_kernel + adjoint + neighbour probes" : "overlap solve + adjoint + neighbour probes";
-    GradPass gp;
-    if (int e = enqueue_gradient_kernels(c, T, kind, P, d_src, h, grad_rounds, grad_tol, warm, true, mask, beside_dev, false, gp, adaptive ? dv.tolarr : nullptr)) return e;
-    HIP_TRY(timer.stop());
-    c->launches++;
-    warm = true;
-    c->grad_warm_T = T;
-    return QMPS_OK;
-  };
-  bool head_done = false;      // the head of this time step (references, first evaluation, begin) already ran behind the previous step's chain
-  for (int step = 0; step < n_steps && rc == QMPS_OK && dev_algebra; ++step) {
-    const bool reset_h = !(carry && (step > 0 || ((flags & QMPS_BFGS_WARM) != 0 && hinv)));
-    if (time_steps) HIP_TRY(hipEventRecord(c->step_ev0, c->stream));
-    if (!head_done) {
-      HIP_TRY(qmps::launch_ansatz(c->D, kind, dv.X, P, c->d_ref, T, c->stream));        // the step's references: A_t = tensor(current parameters)
-      c->overlap_refs = T;
-      c->overlap_group = 0;
-      if ((rc = dev_gradient(dv.X, nullptr))) break;
-      if ((rc = launch_step(step, reset_h, 1))) break;      // f, g, active set; the first direction
-    }
-    head_done = false;
-    n_grad += 1.0;
-    nfev += (double)T * (2 * P + 1);
-    int nit = 0;
-    const qmps::LockstepArgs la = lock_args(step, false, 0);
-    // the ladder of an iteration that stopped on rejected full steps, and what follows it - enqueued only: candidates of every
-    // trajectory, their solves masked by `need` and started from the rejected steps' fixed points, the verdict, the gradient at the
-    // accepted points (masked alike), the update and the next direction (step kernel, mode 3).  Every kernel of it does nothing
-    // when nothing was rejected, so it may be enqueued blindly where the previous time step had a rejection.
-    auto enqueue_ladder = [&]() -> int {
-      if (G <= 0) return fail(QMPS_ERR_ARG, "a rejected full step needs a ladder (n_alphas >= 2)");
-      HIP_TRY(qmps::launch_lockstep_ladder_cand(la, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->d_active, dv.need, (size_t)T, hipMemcpyDeviceToDevice, c->stream));
-      c->mask_stash_n = 0; c->mask_host = nullptr; c->active_n = T;
-      c->ans_have = true; c->ans_kind = kind; c->ans_P = P; c->ans_src = dv.cand; c->ans_i = nullptr; c->ans_nsh = 0;
-      c->tensors_valid = false; c->n_states = T * G; c->window = 0;
-      c->overlap_group = G;
-      c->warm_from_group = (c->grad_warm_T == T) ? G : 0;      // (resident: the fixed points of the rejected full steps)
-      const int e = qmps_overlap_launch(c, T * G, ladder_rounds, tol, 0);
-      c->overlap_group = 0;
-      c->ans_have = false; c->ans_src = nullptr; c->tensors_valid = false; c->n_states = 0;
-      if (e) return e;
-      HIP_TRY(qmps::launch_lockstep_ladder_pick(la, c->d_f, c->d_status, c->stream));
-      if (int e2 = dev_gradient(dv.Xc, dv.need)) return e2;
-      return launch_step(step, false, 3);
-    };
-    bool first_chain = true;
-    for (;;) {
-      // with counters: one iteration per chain, so that every evaluation's event pair can be read (the timed region runs without)
-      int K = per_eval ? 1 : (first_chain ? (chain_fixed > 0 ? chain_fixed : nit_prev) : 1);
-      K = K < 1 ? 1 : K;
-      K = K < maxiter - nit ? K : maxiter - nit;
-      const bool spec_ok = first_chain && !counters_out && documented_switch("QMPS_EVOLVE_SPECULATIVE_HEAD") != nullptr;
-      first_chain = false;
-      for (int i = 0; i < K; ++i) {
-        if ((rc = dev_gradient(dv.Xc, dv.eff))) break;
-        if ((rc = launch_step(step, false, 0))) break;               // finish the iteration, open the next
-        // the previous time step had a rejection at this iteration: its ladder rides along (empty launches if nothing is rejected now)
-        if (!per_eval && (size_t)(nit + i) < rej_prev.size() && rej_prev[nit + i] && (rc = enqueue_ladder())) break;
-      }
-      if (rc) break;
-      // (QMPS_EVOLVE_SPECULATIVE_HEAD; off by default: measured 0.598 against 0.602 ms per time step carried, 3.7 against 3.2 ms identity
-      // start - the host is back and enqueueing before the device has drained the chain, so there is no gap to fill)
-      // the NEXT time step's head behind this chain, masked by "this time step has finished" (head_mask / ctl[5], written by the step
-      // kernel that ends it): when the chain was long enough - the rule - the device goes on without waiting for the host to find out;
-      // otherwise every kernel of it returns at once
-      const bool spec = spec_ok && step + 1 < n_steps;
-      if (spec) {
-        HIP_TRY(qmps::launch_ansatz_masked(c->D, kind, dv.X, P, c->d_ref, T, dv.head, c->stream));
-        if ((rc = dev_gradient(dv.X, dv.head))) break;
-        if ((rc = launch_step(step + 1, !carry, 4))) break;
-      }
-      if (time_steps) HIP_TRY(hipEventRecord(c->step_ev1, c->stream));
-      const size_t n_read = 16 + 2 * ((size_t)maxiter + 2);
-      HIP_TRY(hipMemcpyAsync(c->h_ctl, dv.ctl, n_read * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      const int* hist = c->h_ctl + 16 + ((step + 1) & 1) * (maxiter + 2);
-      const bool finished = c->h_ctl[5] == step + 1;
-      // (finished with a speculative head behind it: the control word already describes the NEXT time step)
-      const int n_act = finished ? 0 : c->h_ctl[0], nit_dev = finished ? c->h_ctl[6] : c->h_ctl[2], stop = finished ? 0 : c->h_ctl[3];
-      if (per_eval && K > 0) {
-        float ms = 0.f;
-        if ((nit_dev > nit || stop) && qmps_kernel_time(c, 1, &ms, nullptr, 0) == QMPS_OK) grad_ms += ms;
-      }
-      if (per_eval) {       // (K = 1: exact counts, as the host loop's)
-        n_grad += (double)(nit_dev - nit) + (stop ? 1.0 : 0.0);
-        nfev += ((double)(nit_dev - nit) + (stop ? 1.0 : 0.0)) * (double)T * (2 * P + 1);
-      }
-      nit = nit_dev;
-      if (finished) {
-        head_done = spec;
-        rej_prev.assign((size_t)nit, 0);
-        for (int i = 0; i < nit; ++i) rej_prev[i] = hist[i] > 0 ? 1 : 0;
-        break;
-      }
-      if (stop) {
-        // some trajectories rejected the full step and no ladder was waiting: enqueue it now (no further synchronisation - the
-        // next chain follows at once)
-        if ((rc = enqueue_ladder())) break;
-        if (time_steps) HIP_TRY(hipEventRecord(c->step_ev1, c->stream));
-        if (per_eval) {
-          HIP_TRY(hipStreamSynchronize(c->stream));
-          float ms = 0.f;
-          if (qmps_kernel_time(c, 1, &ms, nullptr, 0) == QMPS_OK) grad_ms += ms;
-          n_ladder += 1.0;
-          n_grad += 1.0;
-          nfev += (double)T * G + (double)T * (2 * P + 1);
-        }
-        nit += 1;            // (the step kernel of mode 3 counts it on the device; the next read-back finds the step finished or not)
-        continue;
-      }
-      if (n_act == 0 || nit >= maxiter) break;
-    }
-    if (rc) break;
-    if (time_steps) {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, c->step_ev0, c->step_ev1));
-      grad_ms += ms;
-    }
-    // (the step's record - objective at the end, parameters - was written by the last live step kernel; on the device until the call ends)
-    nit_prev = nit > 0 ? nit : 1;
-    if (nit_out) nit_out[step] = nit;
-  }
-  if (dev_algebra) {
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    std::vector<double> fh((size_t)n_steps * 2 * T), ph(params_hist ? (size_t)n_steps * TP : 0);
-    HIP_TRY(hipMemcpyAsync(fh.data(), dv.fh, fh.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (params_hist) HIP_TRY(hipMemcpyAsync(ph.data(), dv.ph, ph.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(X.data(), dv.X, TP * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(Hinv.data(), dv.H, TP * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int step = 0; step < n_steps; ++step) {
-      memcpy(f_hist + (size_t)step * 2 * T_hist + t_off, &fh[(size_t)step * 2 * T], (size_t)T * sizeof(double));
-      memcpy(f_hist + ((size_t)step * 2 + 1) * T_hist + t_off, &fh[((size_t)step * 2 + 1) * T], (size_t)T * sizeof(double));
-      if (params_hist) memcpy(params_hist + ((size_t)step * T_hist + t_off) * P, &ph[(size_t)step * TP], TP * sizeof(double));
-    }
-    c->window = 0;
-    c->have_env = false; c->have_guess = false; c->have_overlap_x = false; c->acc_pending = false; c->partials_B = -1;
-  }
-  for (int step = 0; step < n_steps && rc == QMPS_OK && !dev_algebra; ++step) {
+  for (int step = 0; step < job.n_steps && rc == QMPS_OK; ++step) {
     // the step's references: A_t = tensor(current parameters)
     {
       Restore<bool> deferred(c->defer_sync, true);
-      if ((rc = qmps_overlap_set_refs_ansatz(c, T, kind, P, X.data(), WW))) break;
+      if ((rc = qmps_overlap_set_refs_ansatz(c, T, kind, P, X.data(), job.WW))) break;
     }
-    if (!(carry && (step > 0 || (warm && hinv))))
-      for (int64_t t = 0; t < T; ++t) set_identity(t);
+    if (!(run.carry && (step > 0 || (warm && job.hinv))))
+      for (int64_t t = 0; t < T; ++t) set_identity(Hinv, t, P);
     if (adaptive)      // first evaluation of a time step: by the gradient the previous step's first evaluation found (first step: the tightest)
       for (int64_t t = 0; t < T; ++t) tolv[t] = tol_rule(g0max_prev[t], false);
     if ((rc = value_and_grad(X.data(), f.data(), g.data(), nullptr))) break;
@@ -420,7 +414,7 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
         const double m = gmax_of(&g[(size_t)t * P], isn);
         g0max_prev[t] = isn ? 0.0 : m;
       }
-    memcpy(f_hist + (size_t)step * 2 * T_hist + t_off, f.data(), (size_t)T * sizeof(double));          // objective at the start of the time step
+    memcpy(job.f_hist + (size_t)step * 2 * job.T_hist + job.t_off, f.data(), (size_t)T * sizeof(double));          // objective at the start of the time step
     bool any_active = false;
     for (int64_t t = 0; t < T; ++t) { active[t] = gmax_at_least(&g[(size_t)t * P], gtol) ? 1 : 0; any_active |= active[t] != 0; }
     int nit = 0;
@@ -442,7 +436,7 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
         }
         for (int a = 0; a < P; ++a) sl += gt[a] * dt[a];
         if (!(sl < 0.0)) {                                  // not a descent direction: restart from steepest descent
-          set_identity(t);
+          set_identity(Hinv, t, P);
           sl = 0.0;
           for (int a = 0; a < P; ++a) { dt[a] = -gt[a]; sl -= gt[a] * gt[a]; }
         }
@@ -485,7 +479,7 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
         if ((rc = qmps_overlap_set_group(c, G))) break;
         if ((rc = qmps_overlap_set_active(c, T, need.data()))) break;
         c->warm_from_group = (two_sided && c->grad_warm_T == T) ? G : 0;      // (resident: the fixed points of the rejected full steps)
-        rc = qmps_overlap_eval_ansatz(c, T * G, kind, P, cand.data(), ladder_rounds, tol, 0, Fl.data(), stl.data());
+        rc = qmps_overlap_eval_ansatz(c, T * G, kind, P, cand.data(), run.ladder_rounds, tol, 0, Fl.data(), stl.data());
         (void)qmps_overlap_set_group(c, 0);
         if (rc) break;
         n_ladder += 1.0;
@@ -552,14 +546,63 @@ int evolve_bfgs_group(qmps_ctx* c, int64_t T, int64_t T_hist, int64_t t_off, int
       ++nit;
     }
     if (rc) break;
-    memcpy(f_hist + ((size_t)step * 2 + 1) * T_hist + t_off, f.data(), (size_t)T * sizeof(double));     // ... and at its end
-    if (params_hist) memcpy(params_hist + ((size_t)step * T_hist + t_off) * P, X.data(), TP * sizeof(double));
-    if (nit_out) nit_out[step] = nit;
+    memcpy(job.f_hist + ((size_t)step * 2 + 1) * job.T_hist + job.t_off, f.data(), (size_t)T * sizeof(double));     // ... and at its end
+    if (job.params_hist) memcpy(job.params_hist + ((size_t)step * job.T_hist + job.t_off) * P, X.data(), TP * sizeof(double));
+    if (job.nit_out) job.nit_out[step] = nit;
   }
-  if (rc) return rc;
-  memcpy(params, X.data(), TP * sizeof(double));
-  if (hinv) memcpy(hinv, Hinv.data(), TP * P * sizeof(double));
-  if (counters_out) { counters_out[0] = n_grad; counters_out[1] = n_ladder; counters_out[2] = nfev; counters_out[3] = grad_ms; }
+  return rc;
+}
+
+// The shared front of both paths (argument checks, derived settings, the initial H^-1) and their shared write-back.  May throw
+// (std::vector): the callers catch.
+int evolve_bfgs_group(const BfgsGroup& job) {
+  qmps_ctx* c = job.c;
+  if (int rc = bind(c)) return rc;
+  DisarmOneShots disarm{c};      // nothing armed by this driver outlives it, whichever way it ends
+  if (!job.params || !job.WW || !job.f_hist || !job.alphas) return fail(QMPS_ERR_ARG, "null argument");
+  const int flags = job.flags, max_rounds = job.max_rounds;
+  const double tol = job.tol;
+  if (flags & ~(QMPS_BFGS_CARRY_HESSIAN | QMPS_BFGS_WARM | QMPS_BFGS_TIGHT_GRADIENT | QMPS_BFGS_ADAPTIVE_GRADIENT | QMPS_BFGS_TIME_STEPS)) return fail(QMPS_ERR_ARG, "unknown flag bits 0x%x", flags);
+  const int64_t T = job.T;
+  const int P = job.P, NA = job.NA;
+  if (NA < 1 || NA > 64) return fail(QMPS_ERR_ARG, "n_alphas outside [1, 64]");
+  const int64_t G = NA - 1;
+  if (T < 1 || T * (1 + 2 * (int64_t)P) > c->max_batch || T * G > c->max_batch)
+    return fail(QMPS_ERR_ARG, "T max(2 n_params + 1, n_alphas - 1) = %lld evaluations exceed max_batch = %lld",
+                (long long)(T * ((1 + 2 * (int64_t)P) > G ? (1 + 2 * (int64_t)P) : G)), (long long)c->max_batch);
+  if (job.n_steps < 1 || job.maxiter < 0 || !(job.gtol > 0.0) || !(job.h > 0.0)) return fail(QMPS_ERR_ARG, "bad n_steps / maxiter / gtol / h");
+  if (int rc = check_ansatz(c, job.kind, P)) return rc;
+  const bool carry = (flags & QMPS_BFGS_CARRY_HESSIAN) != 0;
+  const bool warm = (flags & QMPS_BFGS_WARM) != 0;
+  const bool two_sided = c->D >= 4;       // D = 2: the 2 P + 1 central-difference candidates are eigen-solved themselves (a lane each)
+  if (warm && two_sided && c->grad_warm_T != T) return fail(QMPS_ERR_STATE, "QMPS_BFGS_WARM: the resident fixed points belong to %lld trajectories, not %lld", (long long)c->grad_warm_T, (long long)T);
+  const bool squaring = overlap_squares(c);
+  const int ladder_rounds = squaring ? (max_rounds > 60 ? 60 : max_rounds) : max_rounds;
+  const int grad_rounds = max_rounds > 100000 ? max_rounds : 100000;       // (as _GroupedObjective.value_and_grad)
+  // objective by the two-sided quotient (error ~ residual^2): the gradient batches' solves stop at 1e-8 (see qmps_hip.h)
+  double grad_tol = (flags & QMPS_BFGS_TIGHT_GRADIENT) ? tol : (tol > 1e-8 ? tol : 1e-8);
+  if (const char* e = tuning_knob("QMPS_GRAD_TOL")) grad_tol = atof(e);      // (tuning builds: profiles/EXPERIMENTS.md round 5)
+  // QMPS_BFGS_ADAPTIVE_GRADIENT (D = 8, 16): the solves of a trajectory's gradient stop at clamp(1e-3 max|g|, grad_tol, 1e-6), g the
+  // trajectory's current gradient (first evaluation of a time step: the gradient the previous step's first evaluation found; first
+  // step of a call: grad_tol).  The objective still comes from the two-sided quotient (error ~ residual^2 <= 1e-12, far inside the
+  // Armijo margin c1 |slope|: 1e-6 |g|^2 against 1e-4 |g|^2); the gradient carries a relative error <= ~1e-3.
+  const bool adaptive = (flags & QMPS_BFGS_ADAPTIVE_GRADIENT) != 0 && (flags & QMPS_BFGS_TIGHT_GRADIENT) == 0 && two_sided && (c->D == 8 || c->D == 16);
+  const double tol_min = grad_tol, tol_max = grad_tol > 1e-6 ? grad_tol : 1e-6, tol_rel = 1e-3;
+  const size_t TP = (size_t)T * P;
+  BfgsRun run{carry, warm, two_sided, adaptive, ladder_rounds, grad_rounds, grad_tol, tol_min, tol_max, tol_rel, G, TP,
+              std::vector<double>(job.params, job.params + TP), std::vector<double>(TP * P)};
+  // (a pair of event records around a batch costs the stream ~12 us: only when asked for; restored on EVERY way out of this function)
+  Restore<int> period_guard(c->timing_period, job.counters_out ? 1 : 0);
+  Restore<bool> stash_guard(c->stash_masks, true);          // (every batch below ends with a synchronisation)
+  if (carry && warm && job.hinv) memcpy(run.Hinv.data(), job.hinv, TP * P * sizeof(double));
+  else for (int64_t t = 0; t < T; ++t) set_identity(run.Hinv, t, P);
+  // D = 8, 16: the algebra between two evaluations in kernels; QMPS_EVOLVE_HOST_ALGEBRA selects the host loop for everything
+  const bool dev_algebra = two_sided && (c->D == 8 || c->D == 16) && P <= 32 && T <= 65535 && job.maxiter <= 480 && documented_switch("QMPS_EVOLVE_HOST_ALGEBRA") == nullptr &&
+                           documented_switch("QMPS_D16_BLOCK") == nullptr && documented_switch("QMPS_D16_ONE_WAVE") == nullptr;
+  if (int rc = dev_algebra ? evolve_bfgs_device_algebra(job, run) : evolve_bfgs_host_loop(job, run)) return rc;
+  memcpy(job.params, run.X.data(), TP * sizeof(double));
+  if (job.hinv) memcpy(job.hinv, run.Hinv.data(), TP * P * sizeof(double));
+  if (job.counters_out) { job.counters_out[0] = run.n_grad; job.counters_out[1] = run.n_ladder; job.counters_out[2] = run.nfev; job.counters_out[3] = run.grad_ms; }
   return QMPS_OK;
 }
 
@@ -605,9 +648,9 @@ int qmps_evolve_bfgs(qmps_ctx* c, int64_t T, int kind, int n_params, double* par
   // a continued evolution goes where its resident fixed points are: the groups' contexts if the previous call was grouped the same way
   // (group 0 runs on THIS context, groups 1 .. K-1 on contexts of their own)
   const bool groups_warm = (int)c->lockstep.size() == K - 1 && c->lockstep_T == T;
-  if (K <= 1 || (warm && !groups_warm))
-    return evolve_bfgs_group(c, T, T, 0, kind, n_params, params, WW, n_steps, maxiter, gtol, h, c1, n_alphas, alphas, flags, max_rounds, tol, hinv, params_hist,
-                             f_hist, nit_out, counters_out);
+  const BfgsGroup whole{c, T, T, 0, kind, n_params, params, WW, n_steps, maxiter, gtol, h, c1, n_alphas, alphas, flags, max_rounds, tol, hinv, params_hist,
+                        f_hist, nit_out, counters_out};
+  if (K <= 1 || (warm && !groups_warm)) return evolve_bfgs_group(whole);
   // K independent lock-step groups: a context (its own stream and resident buffers) and a host thread each.  While one group's
   // host arithmetic runs, the other groups' kernels do; a straggler holds back its own group only.
   const int P = n_params;
@@ -637,10 +680,16 @@ int qmps_evolve_bfgs(qmps_ctx* c, int64_t T, int kind, int n_params, double* par
   std::vector<int32_t> nits((size_t)K * n_steps, 0);
   std::vector<double> cnts((size_t)K * 4, 0.0);
   auto run = [&](int k) {
+    BfgsGroup group = whole;          // group k: its context, its trajectories, its rows
+    group.c = k == 0 ? c : c->lockstep[k - 1];
+    group.T = off[k + 1] - off[k];
+    group.t_off = off[k];
+    group.params = params ? params + off[k] * P : nullptr;
+    group.hinv = hinv ? hinv + off[k] * P * P : nullptr;
+    group.nit_out = &nits[(size_t)k * n_steps];
+    group.counters_out = counters_out ? &cnts[(size_t)k * 4] : nullptr;
     try {
-      rcs[k] = evolve_bfgs_group(k == 0 ? c : c->lockstep[k - 1], off[k + 1] - off[k], T, off[k], kind, P, params ? params + off[k] * P : nullptr, WW, n_steps, maxiter, gtol, h, c1, n_alphas,
-                                 alphas, flags, max_rounds, tol, hinv ? hinv + off[k] * P * P : nullptr, params_hist, f_hist, &nits[(size_t)k * n_steps],
-                                 counters_out ? &cnts[(size_t)k * 4] : nullptr);
+      rcs[k] = evolve_bfgs_group(group);
     } catch (const std::exception& ex) {
       rcs[k] = fail(QMPS_ERR_ARG, "C++ exception inside the library: %s", ex.what());
     } catch (...) {
@@ -772,7 +821,8 @@ int qmps_evolve_bfgs_device(qmps_ctx* c, int64_t T, int kind, int n_params, doub
     for (int64_t t = 0; t < T; ++t) { a0 += nfev[t]; a1 += nfail[t]; a3 += nfev[T + t]; }
     counters_out[0] = a0; counters_out[1] = a1; counters_out[2] = ms; counters_out[3] = a3;
   }
-  c->have_env = false; c->have_guess = false; c->have_overlap_x = false; c->acc_pending = false; c->partials_B = -1; c->grad_warm_T = 0;
+  forget_resident_state(c);
+  c->grad_warm_T = 0;
   return QMPS_OK;
 }
 QMPS_API_CATCH
@@ -834,7 +884,7 @@ int qmps_evolve_rotosolve(qmps_ctx* c, int64_t T, int kind, int n_params, double
     if (int e = set_ww(c, WW)) return e;
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->window = 0;
-    c->have_env = false; c->have_guess = false; c->have_overlap_x = false; c->acc_pending = false; c->partials_B = -1;
+    forget_resident_state(c);
     c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
     auto evaluate = [&](int shifts) -> int {      // shifts = nsh: the shifted batch of parameter *d_idx;  0: the T base vectors
       const int64_t n = shifts > 0 ? (int64_t)shifts * T : T;

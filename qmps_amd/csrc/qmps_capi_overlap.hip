@@ -379,17 +379,30 @@ int qmps_overlap_eval_ansatz(qmps_ctx* c, int64_t B, int kind, int n_params, con
 QMPS_API_CATCH
 
 namespace qmps_host {
+NeighbourBuild neighbour_build(const qmps_ctx* c, int64_t T, int kind, int P) {
+  // D = 16, ShallowCNOT families: by the surplus workgroups of the pair launch (round 5; not with the kernels of QMPS_D16_BLOCK and
+  // QMPS_D16_ONE_WAVE) - no second stream and none of its two cross-stream dependencies (~7 us each per evaluation)
+  if (qmps::neighbour_build_in_pair(c->D, kind, P) && documented_switch("QMPS_D16_BLOCK") == nullptr && documented_switch("QMPS_D16_ONE_WAVE") == nullptr)
+    return NeighbourBuild::InPair;
+  // otherwise on a second stream BESIDE the eigen-solves: they need the parameters only (at small T a gradient batch is the latency
+  // of its slowest solve; the neighbour tensors were a fifth of it in front of the probes)
+  // (beyond ~1 000 iterates the solves fill the chip by themselves: T = 2 048 measured 5 % slower with the second stream)
+  // (a lock-step group of qmps_evolve_bfgs keeps to ONE stream: the other groups fill the chip, and two streams of one group that
+  // land on the same hardware queue serialise - measured 5-10 % slower and erratic, profiles/EXPERIMENTS.md round 4)
+  return T <= 1024 && !c->one_stream ? NeighbourBuild::Beside : NeighbourBuild::Inline;
+}
+
 // One gradient evaluation of T iterates, ENQUEUED on the context stream and nothing else: [right + left fixed points] beside [the
 // 2 P central-difference neighbours' tensors], then [G + probes].  The iterates' tensors are in d_A[0, T), their parameter rows at
-// d_src (device).  `beside`: the neighbour tensors are built on the second stream, which waits for c->aux_fork - the caller records
-// it on c->stream once d_src is complete.  allow_lazy_krylov: the Krylov fall-back of the two solves is NOT launched behind the
-// power kernels (the caller looks at the statuses on the host and asks for the second pass); otherwise it always runs (it costs an
-// empty launch when nothing was handed over) and the statuses behind this function are final.
+// d_src (device).  Where the neighbour tensors are built: neighbour_build; NeighbourBuild::Beside waits for c->aux_fork on the
+// second stream - the caller records it on c->stream once d_src is complete.  allow_lazy_krylov: the Krylov fall-back of the two
+// solves is NOT launched behind the power kernels (the caller looks at the statuses on the host and asks for the second pass);
+// otherwise it always runs (it costs an empty launch when nothing was handed over) and the statuses behind this function are final.
 // Outputs: d_f[0, T) objective of the iterates, d_f[T, T + 2 P T) of the neighbours, d_status[0, T) / [T, 2 T) right / left solves,
 // d_r / d_y the fixed points (the next call's warm start).  Shared by qmps_overlap_gradient (host loop) and the device-resident
 // lock-step BFGS of qmps_evolve_bfgs.
 int enqueue_gradient_kernels(qmps_ctx* c, int64_t T, int kind, int P, const double* d_src, double h, int max_rounds, double tol, bool warm, bool two_sided_f,
-                             const unsigned char* mask, bool beside, bool allow_lazy_krylov, GradPass& gp, const double* tol_in) {
+                             const unsigned char* mask, bool allow_lazy_krylov, GradPass& gp, const double* tol_in) {
   const bool squaring = overlap_squares(c);       // D = 4: the right fixed point comes from the squaring kernel (largest column)
   qmps::OverlapArgs& a = gp.a;
   memset(&a, 0, sizeof(a));
@@ -403,10 +416,7 @@ int enqueue_gradient_kernels(qmps_ctx* c, int64_t T, int kind, int P, const doub
   // batch of 256 iterates - which never hands anything over - an empty launch and a launch gap, ~10 us of ~200.
   bool lazy_krylov = false;
   const size_t nD = (size_t)c->D * c->D;
-  // where the 2 P central-difference neighbours' tensors come from (D = 16, ShallowCNOT families; see include/qmps_hip.h)
-  const bool fused_probe = qmps::overlap_probe_fusable(c->D, kind, P) && documented_switch("QMPS_FUSED_PROBE") != nullptr;
-  const bool built_in_pair = !fused_probe && qmps::neighbour_build_in_pair(c->D, kind, P) && documented_switch("QMPS_NEIGHBOURS_BESIDE") == nullptr;
-  bool neighbours_done = false;
+  const NeighbourBuild nbuild = neighbour_build(c, T, kind, P);
   // the left fixed points: power method on the adjoint map; results behind the iterates' (eta, rounds, status at [T, 2T))
   qmps::OverlapArgs& l = gp.l;
   l = a;
@@ -421,15 +431,13 @@ int enqueue_gradient_kernels(qmps_ctx* c, int64_t T, int kind, int P, const doub
     if (int e = arm_krylov(c, a, 0)) return e;
     if (int e = arm_krylov(c, l, 1)) return e;
     lazy_krylov = allow_lazy_krylov && a.krylov_after > 0 && l.krylov_after > 0 && a.kry_counter != nullptr && l.kry_counter != nullptr;
-    // ... and the central-difference neighbours' tensors by the surplus workgroups of the same launch (ShallowCNOT families;
-    // QMPS_NEIGHBOURS_BESIDE: the round-4 kernel on the second stream, QMPS_FUSED_PROBE: inside the probe kernel)
+    // ... and the central-difference neighbours' tensors by the surplus workgroups of the same launch (ShallowCNOT families)
     qmps::NeighbourBuildArgs nb;
     memset(&nb, 0, sizeof(nb));
-    if (built_in_pair) {
+    if (nbuild == NeighbourBuild::InPair) {
       nb.params = d_src; nb.out = (char*)c->d_A + (size_t)T * tensor_bytes(c); nb.rows = T; nb.n_params = P; nb.kind = kind; nb.h = h; nb.active = mask;
     }
-    HIP_TRY(qmps::launch_overlap_pair_d16(a, l, c->stream, !lazy_krylov, built_in_pair ? &nb : nullptr));
-    neighbours_done = built_in_pair;
+    HIP_TRY(qmps::launch_overlap_pair_d16(a, l, c->stream, !lazy_krylov, nbuild == NeighbourBuild::InPair ? &nb : nullptr));
   } else if (c->D == 8) {
     // D = 8: the same - one launch, the left solves on the SIMDs the right ones leave idle
     a.no_deflation = l.no_deflation = documented_switch("QMPS_NO_DEFLATION") != nullptr ? 1 : 0;
@@ -449,20 +457,19 @@ int enqueue_gradient_kernels(qmps_ctx* c, int64_t T, int kind, int P, const doub
     l.no_deflation = documented_switch("QMPS_NO_DEFLATION") != nullptr ? 1 : 0;
     HIP_TRY(qmps::launch_overlap_d(c->D, l, c->D == 4 ? squaring : (c->D == 16 && documented_switch("QMPS_D16_BLOCK") == nullptr), c->stream));
   }
-  if (fused_probe || neighbours_done) {
-  } else if (beside) {
+  if (nbuild == NeighbourBuild::Beside) {
     HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->aux_fork, 0));
     HIP_TRY(qmps::launch_ansatz_fd(c->D, kind, d_src, P, (char*)c->d_A + (size_t)T * tensor_bytes(c), T, h, c->aux_stream, mask));
     HIP_TRY(hipEventRecord(c->aux_join, c->aux_stream));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->aux_join, 0));
+  } else if (nbuild == NeighbourBuild::Inline) {
+    HIP_TRY(qmps::launch_ansatz_fd(c->D, kind, d_src, P, (char*)c->d_A + (size_t)T * tensor_bytes(c), T, h, c->stream, mask));
   }
-  else HIP_TRY(qmps::launch_ansatz_fd(c->D, kind, d_src, P, (char*)c->d_A + (size_t)T * tensor_bytes(c), T, h, c->stream, mask));
   qmps::OverlapGradArgs& g = gp.g;
   memset(&g, 0, sizeof(g));
   g.A = c->d_ref; g.WW = c->d_ww; g.r = c->d_r; g.y = c->d_y; g.G = c->d_scratch; g.yr = (char*)c->d_scratch + (size_t)T * 4 * nD * 16;
   g.Bt = (char*)c->d_A + (size_t)T * tensor_bytes(c); g.f_out = c->d_f + T; g.T = T; g.G2P = 2 * P; g.active = mask;
   if (two_sided_f) { g.Bc = c->d_A; g.fc_out = c->d_f; }       // (overwrites the right solve's own estimate)
-  if (fused_probe) { g.fd_params = d_src; g.fd_h = h; g.kind = kind; }
   HIP_TRY(qmps::launch_overlap_grad(c->D, g, c->stream));
   gp.lazy_krylov = lazy_krylov;
   return QMPS_OK;
@@ -491,21 +498,13 @@ int qmps_overlap_gradient(qmps_ctx* c, int64_t T, int kind, int n_params, const 
     const size_t need = (size_t)T * (1 + 2 * P) * sizeof(double) + (size_t)2 * T * sizeof(int32_t) + (8u << 20);
     if (int e = ensure_pinned(c, need > (16u << 20) ? need : (16u << 20))) return e;
   }
-  // the 2 P central-difference neighbours of every iterate (evaluated below to second order in h from (y, r)): their tensors
-  // need the parameters only, so they are built on a second stream BESIDE the eigen-solves (at small T a gradient batch is the
-  // latency of its slowest solve; the neighbour tensors were a fifth of it in front of the probes)
+  // the 2 P central-difference neighbours of every iterate (evaluated below to second order in h from (y, r)): neighbour_build
   if (!c->aux_stream) {
     HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
   }
-  // (beyond ~1 000 iterates the solves fill the chip by themselves: T = 2 048 measured 5 % slower with the second stream)
-  // (a lock-step group of qmps_evolve_bfgs keeps to ONE stream: the other groups fill the chip, and two streams of one group that
-  // land on the same hardware queue serialise - measured 5-10 % slower and erratic, profiles/EXPERIMENTS.md round 4)
-  const bool no_second_stream = (qmps::overlap_probe_fusable(c->D, kind, P) && documented_switch("QMPS_FUSED_PROBE") != nullptr) ||
-                                (qmps::neighbour_build_in_pair(c->D, kind, P) && documented_switch("QMPS_NEIGHBOURS_BESIDE") == nullptr &&
-                                 documented_switch("QMPS_D16_BLOCK") == nullptr && documented_switch("QMPS_D16_ONE_WAVE") == nullptr);
-  const bool beside = T <= 1024 && !c->one_stream && !no_second_stream;
+  const bool beside = neighbour_build(c, T, kind, P) == NeighbourBuild::Beside;
   // the iterates: parameters -> tensors in d_A[0, T); the fork event sits between the parameter upload and the tensor build, and
   // the second stream is fed only AFTER the solves are submitted (the host calls of the fork used to hold the solves back ~15 us)
   int rc;
@@ -536,7 +535,7 @@ int qmps_overlap_gradient(qmps_ctx* c, int64_t T, int kind, int n_params, const 
   GradPass gp;
   const double* tol_in = c->grad_tol_in;        // one-shot (qmps_evolve_bfgs, host loop): per-trajectory tolerances
   c->grad_tol_in = nullptr;
-  if (int e = enqueue_gradient_kernels(c, T, kind, P, c->d_params, h, max_rounds, tol, warm, (flags & QMPS_OVERLAP_TWO_SIDED_F) != 0, mask, beside, true, gp, tol_in)) return e;
+  if (int e = enqueue_gradient_kernels(c, T, kind, P, c->d_params, h, max_rounds, tol, warm, (flags & QMPS_OVERLAP_TWO_SIDED_F) != 0, mask, true, gp, tol_in)) return e;
   const bool lazy_krylov = gp.lazy_krylov;
   qmps::OverlapArgs &a = gp.a, &l = gp.l;
   qmps::OverlapGradArgs& g = gp.g;
@@ -603,7 +602,7 @@ int qmps_overlap_gradient(qmps_ctx* c, int64_t T, int kind, int n_params, const 
         f_out[t] = -__builtin_sqrt(__builtin_sqrt(eta[2 * t] * eta[2 * t] + eta[2 * t + 1] * eta[2 * t + 1]));
   }
   c->window = 0;
-  c->have_env = false; c->have_guess = false; c->have_overlap_x = false; c->acc_pending = false; c->partials_B = -1;
+  forget_resident_state(c);
   c->grad_warm_T = T;
   return QMPS_OK;
 }

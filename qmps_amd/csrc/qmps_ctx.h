@@ -266,6 +266,11 @@ inline int krylov_after() {
 }
 
 int bind(qmps_ctx* c);
+// after an overlap or evolve call: the energy path's resident environments, guesses, fixed points, pending cost and per-wave partial
+// sums no longer describe the buffers
+inline void forget_resident_state(qmps_ctx* c) {
+  c->have_env = false; c->have_guess = false; c->have_overlap_x = false; c->acc_pending = false; c->partials_B = -1;
+}
 inline size_t tensor_bytes(const qmps_ctx* c) { return (size_t)32 * c->D * c->D; }
 inline size_t env_bytes(const qmps_ctx* c) { return (size_t)16 * c->D * c->D; }
 int ensure_scratch(qmps_ctx* c, size_t bytes);

@@ -9,16 +9,17 @@
 // batch (28 % of a time step at 256 trajectories).  The kernel below does that algebra on device-resident x, g, H^-1, so that the
 // host only ENQUEUES: evaluation -> step kernel -> evaluation -> step kernel ...  A control word in HBM tells every kernel of a
 // chain of iterations whether there is anything left to do - no trajectory active, or a trajectory REJECTED the full step (its
-// backtracking ladder is the rare path: the host takes over for that iteration) - so a chain enqueued blindly costs empty
-// launches at its tail, not wrong work.
+// backtracking ladder is the rare path: the ladder kernels below, enqueued behind the chain) - so a chain enqueued blindly costs
+// empty launches at its tail, not wrong work.
 //
 // ONE kernel per iteration: `lockstep_step_kernel` finishes iteration k from its evaluation (phase ACCEPT: Armijo test of the full
 // step, the step, the BFGS update, the new active set) and, when the lock-step goes on, opens iteration k + 1 (phase DIRECTION:
 // d = -H^-1 g, slope, the candidates x + alpha_0 d and the mask of the next evaluation).  MODE_BEGIN replaces the first phase after
-// the first evaluation of a time step (f, g from the batch, the active set, H^-1 = 1 unless carried).
+// the first evaluation of a time step (f, g from the batch, the active set, H^-1 = 1 unless carried); mode 3 finishes an iteration
+// that stopped on rejected full steps once their ladder and the gradient at the accepted points have run.
 //
-// The floating-point expressions are those of the host loop (evolve_bfgs_group, which remains the checker and the path of the
-// ladder), every sum in the same order and WITHOUT contraction: given the same evaluations both take the same decisions bit for bit.
+// The floating-point expressions are those of the host loop (evolve_bfgs_host_loop, which remains the checker), every sum in the
+// same order and WITHOUT contraction: given the same evaluations both take the same decisions bit for bit.
 //
 // Layout: one workgroup of 1024 threads; PL = 2^ceil(log2 P) <= 32 lanes per trajectory (lane a owns component a and row a of
 // H^-1, kept in registers: the P x P work is O(P) per lane with coalesced rows), 1024 / PL trajectories per pass.  Sums over
@@ -67,9 +68,7 @@ __global__ __launch_bounds__(LS_THREADS) void lockstep_step_kernel(LockstepArgs 
   const int P = p.P;
   const bool lane_on = a < P;
   const int n_active0 = p.ctl[0], nit0 = p.ctl[2], stop0 = p.ctl[3];
-  const int done_step = p.ctl[5];
-  const bool speculative = p.mode == 4;
-  const bool begin = p.mode == 1 || speculative, open_only = p.mode == 2, after_ladder = p.mode == 3;
+  const bool begin = p.mode == 1, after_ladder = p.mode == 3;
   // all components of a per-trajectory vector held one component per lane, into registers: PL shuffles issued back to back (every
   // lane of the wave takes part: no divergence around it).  (First version: a shuffle where a component was needed, inside the
   // sequential sums - ~100 dependent LDS-crossbar round trips per pass, 6 us.)
@@ -106,13 +105,12 @@ __global__ __launch_bounds__(LS_THREADS) void lockstep_step_kernel(LockstepArgs 
   // phase 1: ACCEPT (or BEGIN)
   // ---------------------------------------------------------------------------------------------------------------------------
   // mode 3 finishes an iteration that stopped on rejected full steps (their ladder and the gradient at the accepted points have run)
-  // mode 4: the head of a time step enqueued behind the previous step's chain - live only if that step has finished
-  const bool live = speculative ? done_step == p.step_id - 1 : (begin || open_only || (after_ladder ? stop0 != 0 : !(n_active0 == 0 || stop0 != 0 || nit0 >= p.maxiter)));
+  const bool live = begin || (after_ladder ? stop0 != 0 : !(n_active0 == 0 || stop0 != 0 || nit0 >= p.maxiter));
   // (nothing to finish: the mask of the next evaluation stays empty - cleared when the lock-step stopped; the launch still takes part
   // in the barrier below, whose arrival count the host's epoch relies on)
   int n_need = 0, n_active = 0;
   const double nan = __builtin_nan("");
-  for (int base = blockIdx.x * SLOTS; base < p.T && !open_only && live; base += gridDim.x * SLOTS) {
+  for (int base = blockIdx.x * SLOTS; base < p.T && live; base += gridDim.x * SLOTS) {
     const int t = base + slot;
     const bool on = t < p.T;
     const int ts = on ? t : 0;
@@ -213,7 +211,7 @@ __global__ __launch_bounds__(LS_THREADS) void lockstep_step_kernel(LockstepArgs 
         p.F0[t] = Ft0;                                   // rung 0 of its ladder
         p.need[t] = 1;
         n_need += 1;
-        n_active += 1;                                   // (still active until the host has finished its iteration)
+        n_active += 1;                                   // (still active until its ladder has finished the iteration)
       } else {
         if (moved) p.F[t] = fs;                          // (mode 0: finite; mode 3: NaN if the solve at the accepted point failed)
         p.active[t] = act ? 1 : 0;
@@ -251,10 +249,9 @@ __global__ __launch_bounds__(LS_THREADS) void lockstep_step_kernel(LockstepArgs 
       p.ctl[9 + 2 * (e ^ 1)] = 0;
     }
   }
-  if (open_only) n_active = n_active0;                   // (the host finished the iteration and wrote the control word)
-  const int nit = open_only ? nit0 : (begin ? 0 : (n_need > 0 ? nit0 : nit0 + 1));           // (mode 3: n_need = 0, the iteration is complete)
-  const int stop = open_only ? stop0 : (n_need > 0 ? 1 : 0);
-  if (blockIdx.x == 0 && threadIdx.x == 0 && !open_only && live) {
+  const int nit = begin ? 0 : (n_need > 0 ? nit0 : nit0 + 1);           // (mode 3: n_need = 0, the iteration is complete)
+  const int stop = n_need > 0 ? 1 : 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && live) {
     p.ctl[0] = n_active;
     p.ctl[1] = n_need;
     p.ctl[2] = nit;
@@ -270,7 +267,6 @@ __global__ __launch_bounds__(LS_THREADS) void lockstep_step_kernel(LockstepArgs 
   // ---------------------------------------------------------------------------------------------------------------------------
   if (!live) return;
   const bool go_on = n_active > 0 && stop == 0 && nit < p.maxiter;
-  const bool finished = !go_on && stop == 0;
   if (begin && blockIdx.x == 0)      // a new time step: its pattern of rejections starts empty
     for (int k = threadIdx.x; k <= p.maxiter + 1; k += blockDim.x) p.ctl[16 + p.hist_off + k] = 0;
   for (int base = blockIdx.x * SLOTS; base < p.T; base += gridDim.x * SLOTS) {
@@ -286,13 +282,10 @@ __global__ __launch_bounds__(LS_THREADS) void lockstep_step_kernel(LockstepArgs 
     if (go_on)
 #pragma unroll
       for (int b = 0; b < PL; ++b) hrow[b] = (b < P) ? H[as * P + b] : 0.0;
-    // the record of the time step so far (final when the lock-step stops here; a trajectory waiting for the host's ladder is
-    // recorded again by the mode-2 launch that follows the host's update)
+    // the record of the time step so far (final when the lock-step stops here; a trajectory waiting for its ladder is recorded
+    // again by the mode-3 launch that finishes its iteration)
     if (on && lane_on) p.ph[tp + a] = xa;
-    if (on && a == 0) {
-      p.fh_end[t] = Ft;
-      p.head_mask[t] = finished ? 1 : 0;
-    }
+    if (on && a == 0) p.fh_end[t] = Ft;
     if (p.tol_next != nullptr) {
       double gt_all[PL];
       gather(ga, gt_all);

@@ -172,8 +172,6 @@ hipError_t launch_energy(int D, const LaneArgs& a, bool solve, hipStream_t st);
 hipError_t launch_energy_block(int D, const LaneArgs& a, bool solve, hipStream_t st);
 // ansatz parameters [B][n_params] -> state tensors A [B][2][D][D]; kind: 0 ShallowCNOT, 1 QAOA, 2 ShallowFull (D=2), 3 ShallowCNOT3
 hipError_t launch_ansatz(int D, int kind, const double* params, int n_params, void* A, int64_t B, hipStream_t st);
-// ... rows with active[row] == 0 left alone (active nullable)
-hipError_t launch_ansatz_masked(int D, int kind, const double* params, int n_params, void* A, int64_t B, const unsigned char* active, hipStream_t st);
 // the same for rotosolve shift batches: B = nsh R evaluations, evaluation nsh r + k = row r with shift k on parameter *i_ptr
 hipError_t launch_ansatz_shifted(int D, int kind, const double* params, int n_params, void* A, int64_t B, int nsh, const int* i_ptr,
                                  hipStream_t st);
@@ -236,7 +234,7 @@ struct LockstepArgs {
   const int32_t* st;     // ... and statuses: [0, T) right solves, [T, 2 T) left solves
   unsigned char* active; // [T] trajectories still iterating
   unsigned char* eff;    // [T] mask of the next evaluation (active, or all zero when the chain has nothing to do)
-  unsigned char* need;   // [T] rejected the full step: waiting for the host's ladder
+  unsigned char* need;   // [T] rejected the full step: waiting for its ladder
   int* ctl;              // [0] active trajectories, [1] trajectories waiting for the ladder, [2] iterations done, [3] stop;
                          // [16 + k]: trajectories that rejected the full step of iteration k of this time step
   double* fh_start;      // nullable [T]: record of the objective at the start of the time step (mode 1)
@@ -244,12 +242,10 @@ struct LockstepArgs {
   double* ph;            // [T][P] ... and of the parameters
   int T, P, maxiter, reset_h;
   int step_id;           // 1, 2, ...: the time step this launch belongs to (ctl[5] = id of the last finished step, ctl[6] = its iteration count)
-  unsigned char* head_mask;   // [T] 1 everywhere once the time step has finished, else 0: the mask of the NEXT step's speculative head
   int hist_off;          // offset of this time step's rejection pattern in ctl[16 ...] (two regions, alternating)
   int mode;              // 0: finish an iteration from its evaluation, open the next; 1: the same after the FIRST evaluation of a time step
-                         // (f, g, active set from the batch; H^-1 = 1 if reset_h); 2: open the next iteration only (the host has finished one);
-                         // 3: finish an iteration that stopped on rejected full steps, after their ladder and the gradient at the accepted points;
-                         // 4: mode 1 enqueued SPECULATIVELY behind the previous time step's chain - does nothing unless that step has finished
+                         // (f, g, active set from the batch; H^-1 = 1 if reset_h);
+                         // 3: finish an iteration that stopped on rejected full steps, after their ladder and the gradient at the accepted points
   double h, gtol, c1, alpha0;
   // the backtracking ladder of the trajectories that rejected the full step (lockstep_ladder_*_kernel)
   double* F0;            // [T] objective of the rejected full step (rung 0)
@@ -286,15 +282,8 @@ struct OverlapGradArgs {
   const unsigned char* active;   // nullable [T]: 0 = skip the trajectory (outputs keep their previous values)
   const void* Bc;      // nullable [T][2][D][D]: the iterates' own tensors - their objective by the same two-sided quotient
   double* fc_out;      // [T]: -sqrt|<y, T(r)>/<y, r>|  (error ~ the PRODUCT of the residuals of y and r)
-  // D = 16, ShallowCNOT families: the probe kernel BUILDS every neighbour's tensor itself (wave-distributed circuit, LDS) instead of
-  // reading it from Bt - no neighbour tensors in HBM at all.  fd_params != nullptr selects it (overlap_probe_fusable).
-  const double* fd_params;   // nullable [T][G2P / 2] parameter rows of the iterates (device)
-  double fd_h;               // central-difference step: neighbour k < P has +fd_h on parameter k, neighbour P + k has -fd_h
-  int kind;                  // QMPS_ANSATZ_* of the rows
 };
 hipError_t launch_overlap_grad(int D, const OverlapGradArgs& a, hipStream_t st);
-// can the D = 16 probe kernel build the neighbours of this ansatz kind itself?
-inline bool overlap_probe_fusable(int D, int kind, int n_params) { return D == 16 && (kind == 0 || kind == 3) && n_params >= 1 && n_params <= 64; }
 constexpr int kOverlapStatShards = 1024;
 #if defined(__HIPCC__)
 __device__ __forceinline__ int64_t overlap_ref_index(const OverlapArgs& p, int64_t b) { return p.group > 0 ? b / p.group : (p.a_shared ? 0 : b); }

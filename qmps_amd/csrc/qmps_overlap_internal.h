@@ -20,6 +20,11 @@ struct DisarmOneShots {
   ~DisarmOneShots() { c->active_n = 0; c->mask_stash_n = 0; c->mask_host = nullptr; c->fork_after_copy = nullptr; c->warm_from_group = 0; c->grad_tol_in = nullptr; }
 };
 
+// Where a gradient evaluation of T iterates builds the tensors of their 2 P central-difference neighbours: inside the D = 16 pair
+// launch, on the second stream beside the eigen-solves, or on the context stream in front of the probes
+enum class NeighbourBuild { InPair, Beside, Inline };
+NeighbourBuild neighbour_build(const qmps_ctx* c, int64_t T, int kind, int P);
+
 // One gradient evaluation of T iterates, ENQUEUED on the context stream and nothing else (see qmps_capi_overlap.hip)
 struct GradPass {
   qmps::OverlapArgs a, l;
@@ -27,6 +32,6 @@ struct GradPass {
   bool lazy_krylov = false;
 };
 int enqueue_gradient_kernels(qmps_ctx* c, int64_t T, int kind, int P, const double* d_src, double h, int max_rounds, double tol, bool warm, bool two_sided_f,
-                             const unsigned char* mask, bool beside, bool allow_lazy_krylov, GradPass& gp, const double* tol_in = nullptr);
+                             const unsigned char* mask, bool allow_lazy_krylov, GradPass& gp, const double* tol_in = nullptr);
 
 }  // namespace qmps_host
