@@ -71,3 +71,49 @@ def test_fallback_non_isometric_and_degenerate():
     assert out['status'][0] == 2 and abs(out['E'][0, 0] + 1.0) < 1e-12
     E, it, st = O.energy_direct(O.unitary_to_tensor(U)[0], h)
     assert st == 2 and abs(E + 1.0) < 1e-12
+
+
+def test_near_singular_environments_every_status():
+    """The family of tests/conditioning_cases.py at D = 4 through the emulation: the gauged sweep t = 1 .. 1e-9 (19 strengths x 64), the
+    ungauged slice (the elimination is not accepted: the power method 2^m steps at a time) and 512 Haar rows.  r, rho, E (three terms, one
+    not Hermitian) and E_lean of EVERY row of status 0 or 2 against the mpmath reference within 1e-10, rho Hermitian with trace 1 and no
+    eigenvalue below -1e-13, rho against two_site_rdm of the kernel's own r within 1e-13, r against oracle.env_direct within 1e-12 where both
+    accept the solve in one step; status 0 wherever the reference's smallest eigenvalue is >= 1e-13, status 2 only below.  Both routes of
+    DirectD4::density carry weight: among the rows with t <= 3e-5 at least a fifth is status 2 (the Y = B r route) and at least a fifth
+    status 0 (the LDL^H route at pivots of ~1e-16).
+    Measured: r 5.8e-15, rho 6.4e-15, E 1.2e-14, E_lean 1.1e-14, rho against its own r 1.0e-15, r against env_direct 2.8e-15, trace 6.2e-15,
+    smallest eigenvalue of rho -3.2e-15, rho exactly Hermitian; 1 459 rows status 0, 405 status 2, none status 1.
+    With one sign flipped in the LDL^H branch of density() (G_tau = B_tau L) or in its Y = B r branch the assertion
+    `fig['r'] < R_TOL and fig['rho'] < R_TOL and fig['E'] < E_TOL` of conditioning_cases.compare fails (rho off by 0.6 / 0.5, E by 3.0 / 1.3);
+    the second flip passes every other test of this file."""
+    from tests import conditioning_cases as CC
+    fam = CC.family(4)
+    h = CC.hamiltonian_terms()
+    out = EMU.energies_d4(fam['A'], h)
+    CC.compare(4, out, h, 'emulation', one_step=True, rho_self=True)
+    st, it = out['status'], out['iters']
+    assert not np.any(st == 1)
+    assert np.all(it[fam['gauged']] == 1)
+    small = fam['gauged'] & (fam['t'] > 0) & (fam['t'] <= 3e-5)          # the strengths 1e-5 .. 1e-9 of the sweep
+    assert (st[small] == 2).mean() >= 0.2 and (st[small] == 0).mean() >= 0.2, (st[small] == 2).mean()
+    # the ungauged slice leaves the one-step solve (a pivot below 1e-10 without pivoting) and comes back with status 0 or 2 all the same
+    un = ~fam['gauged']
+    assert (it[un] > 1).mean() > 0.5 and np.all(np.log2(it[un & (it > 1)] - 1) % 1 == 0)
+
+
+@pytest.mark.parametrize('D', [2, 4, 8, 16])
+def test_double_precision_references_against_mpmath(D):
+    """oracle.env_direct (pivoted LU) against the mpmath solve of the same system on the rows that have one (tests/conditioning_cases.py):
+    it is the reference of the rows mpmath is too slow for.  1e-13: backward error N eps times the condition number 1 / gap <= ~1e3 of the
+    system.  Measured 7.2e-16, 6.7e-16, 9.4e-16, 9.0e-16 at D = 2, 4, 8, 16 (the dense eigen-solve: 3.7e-12 at D = 2)."""
+    from tests import conditioning_cases as CC
+    fam, ref, dref = CC.family(D), CC.references(D), CC.direct_references(D)
+    ex = np.flatnonzero(fam['exact'])
+    assert all(dref[b][1:] == (1, 0) for b in ex)
+    assert max(np.abs(dref[b][0] - ref['r'][b]).max() for b in ex) < 1e-13
+    assert np.abs(np.einsum('bsij,bsik->bjk', fam['A'].conj(), fam['A']) - np.eye(D)).max() < 1e-13
+    # the reference rho is oracle.two_site_rdm in double on the rounded r: against the same contraction in mpmath on a few rows.  1e-14: entries
+    # of modulus <= 1, sums of at most 2 D^2 products (~50 eps at D = 16).  Measured 5.6e-16 at most.
+    worst = max(np.abs(CC.two_site_rdm_mp(fam['A'][b], ref['r'][b]) - ref['rho'][b]).max() for b in ex[::max(1, len(ex) // 4)][:4])
+    print(f'reference rho against mpmath D={D}: {worst:.2e}')
+    assert worst < 1e-14
