@@ -1,6 +1,6 @@
 // qmps_capi.hip - the C-ABI of libqmps_hip.so (declared in include/qmps_hip.h): library / device, context lifetime, states,
-// the energy path, the rotosolve drivers, read-back, the summed-cost exchange (RCCL), probes.  The time-evolution overlap
-// objective and the evolve drivers: qmps_capi_overlap.hip.  Shared context + helpers: qmps_ctx.h.
+// the energy path, read-back, the summed-cost exchange (RCCL), probes.  The rotosolve drivers: qmps_capi_roto.hip.  The time-evolution
+// overlap objective: qmps_capi_overlap.hip; the evolve drivers: qmps_capi_evolve.hip.  Shared context + helpers: qmps_ctx.h.
 // Host-side runtime: context = one device + one HIP stream + HBM buffers; asynchronous launches;
 // pinned staging for small results; native RCCL communicator for the summed-cost all-reduce.
 #include "qmps_ctx.h"
@@ -528,236 +528,6 @@ int qmps_su_unitaries(qmps_ctx* c, int64_t B, int N, const double* params, doubl
   return QMPS_OK;
 }
 QMPS_API_CATCH
-
-namespace {
-int rotosolve_impl(qmps_ctx* c, int64_t R, int kind, int n_params, double* params, int n_sweeps, int max_iter, double tol,
-                   double* E_hist, int nsh);
-}
-
-int qmps_rotosolve(qmps_ctx* c, int64_t R, int kind, int n_params, double* params, int n_sweeps, int max_iter,
-                   double tol, double* E_hist) try {
-  return rotosolve_impl(c, R, kind, n_params, params, n_sweeps, max_iter, tol, E_hist, 3);
-}
-QMPS_API_CATCH
-
-int qmps_double_rotosolve(qmps_ctx* c, int64_t R, int kind, int n_params, double* params, int n_sweeps, int max_iter,
-                          double tol, double* E_hist) try {
-  return rotosolve_impl(c, R, kind, n_params, params, n_sweeps, max_iter, tol, E_hist, 6);
-}
-QMPS_API_CATCH
-
-namespace {
-int rotosolve_impl(qmps_ctx* c, int64_t R, int kind, int n_params, double* params, int n_sweeps, int max_iter, double tol,
-                   double* E_hist, int nsh) {
-  if (int rc = bind(c)) return rc;
-  if (R < 1 || nsh * R > c->max_batch) return fail(QMPS_ERR_ARG, "%d R = %lld evaluations exceed max_batch = %lld", nsh, (long long)(nsh * R), (long long)c->max_batch);
-  c->window = 0;
-  if (!params || !E_hist) return fail(QMPS_ERR_ARG, "null argument");
-  if (n_sweeps < 1) return fail(QMPS_ERR_ARG, "n_sweeps must be >= 1");
-  if (c->n_terms < 1) return fail(QMPS_ERR_STATE, "qmps_set_hamiltonian has not been called");
-  if (int rc = check_ansatz(c, kind, n_params)) return rc;
-  if (n_params > c->params_cap) {
-    if (c->d_params) HIP_TRY(hipFree(c->d_params));
-    c->d_params = nullptr;
-    HIP_TRY(hipMalloc((void**)&c->d_params, (size_t)c->max_batch * n_params * sizeof(double)));
-    c->params_cap = n_params;
-  }
-  auto grow = [&](double*& buf, size_t& have, size_t need) -> int {
-    if (need > have) {
-      if (buf) HIP_TRY(hipFree(buf));
-      buf = nullptr;
-      have = 0;
-      HIP_TRY(hipMalloc((void**)&buf, need));
-      have = need;
-    }
-    return QMPS_OK;
-  };
-  if (int rc = grow(c->roto_base, c->roto_base_bytes, (size_t)R * n_params * sizeof(double))) return rc;
-  // The run's results (final parameters, energy history) come back through the context's pinned buffer when they fit: the
-  // first LARGE copy into pageable memory makes the runtime set up its internal staging, ~8 ms once per process (measured
-  // in the first 160-sweep call after an 8-sweep one: 27.7 instead of 19.5 us per parameter update at D = 8).
-  auto download_results = [&](size_t hist_doubles) -> int {
-    const size_t pb = (size_t)R * n_params * sizeof(double), hb = hist_doubles * sizeof(double);
-    if (pb + hb <= (2u << 20)) {      // (small results only: a 7 MB history copied twice cost the D = 4 run of 21 845 restarts 16 %)
-      if (int e = ensure_pinned(c, (16u << 20))) return e;
-      HIP_TRY(hipMemcpyAsync(c->h_pin, c->roto_base, pb, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_pin + pb, c->roto_hist, hb, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      memcpy(params, c->h_pin, pb);
-      memcpy(E_hist, c->h_pin + pb, hb);
-      return QMPS_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(params, c->roto_base, pb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(E_hist, c->roto_hist, hb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return QMPS_OK;
-  };
-#ifdef QMPS_D8_PROFILE        // scratch instrumentation build (profiles/experiments/scratch/d8_profile.py): 16 phase clocks behind the history
-  constexpr size_t kHistExtra = 16 + 3 * 4096;
-#else
-  constexpr size_t kHistExtra = 0;
-#endif
-#ifdef QMPS_D8_PROFILE
-  const auto g0 = std::chrono::steady_clock::now();
-#endif
-  if (int rc = grow(c->roto_hist, c->roto_hist_bytes, ((size_t)R * n_sweeps + kHistExtra) * sizeof(double))) return rc;
-#ifdef QMPS_D8_PROFILE
-  fprintf(stderr, "[d8 profile] history buffer: %.0f us\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - g0).count());
-#endif
-  if (!c->roto_idx) HIP_TRY(hipMalloc((void**)&c->roto_idx, 4 * sizeof(int)));
-  double *d_base = c->roto_base, *d_hist = c->roto_hist;
-  int* d_idx = c->roto_idx;
-  int rc = [&]() -> int {
-    HIP_TRY(hipMemcpyAsync(d_base, params, (size_t)R * n_params * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(d_idx, 0, 3 * sizeof(int), c->stream));   // parameter index, arrival counter, finished sweeps
-    if (kHistExtra) HIP_TRY(hipMemsetAsync(d_hist + (size_t)R * n_sweeps, 0, kHistExtra * sizeof(double), c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const bool saved_guess = c->have_guess;
-    c->have_guess = false;
-    // D = 2 with the library's default solver: the whole run is ONE launch (restarts are independent, see
-    // rotosolve_fused_d2_kernel); afterwards one ordinary evaluation of the final parameters leaves the context's
-    // resident tensors / energies / statuses exactly as the step-by-step path does.
-    if ((nsh == 3 || nsh == 6) && c->D == 2 && c->handoff == 0 && (c->default_solver == QMPS_ENV_POWER_SQUARING || c->default_solver == QMPS_ENV_DIRECT) && n_params <= 64 &&
-        documented_switch("QMPS_NO_FUSED_ROTO") == nullptr) {
-      qmps::RotoArgs ra;
-      memset(&ra, 0, sizeof(ra));
-      ra.base = d_base; ra.h = c->d_h; ra.hist = d_hist;
-      ra.R = (int)R; ra.P = n_params; ra.n_terms = c->n_terms; ra.n_sweeps = n_sweeps; ra.max_iter = max_iter;
-      ra.skip = c->skip_rounds; ra.tol = tol; ra.direct = c->default_solver == QMPS_ENV_DIRECT ? 1 : 0; ra.nsh = nsh; ra.rule = c->roto_rule;
-      HIP_TRY(qmps::launch_rotosolve_fused_d2(kind, ra, c->stream));
-      HIP_TRY(qmps::launch_ansatz(c->D, kind, d_base, n_params, c->d_A, R, c->stream));
-      c->n_states = R; c->ans_have = false; c->tensors_valid = true;
-      if (int e = qmps_energy_launch(c, R, max_iter, tol, c->default_solver)) return e;
-      c->have_guess = saved_guess;
-      return download_results((size_t)R * n_sweeps);
-    }
-    // D = 8 (ShallowCNOT families, direct solver): the whole run in ONE launch as well - a workgroup per restart, a wave per
-    // shift (qmps_roto_d8.hip); afterwards one ordinary evaluation of the final parameters, as above
-    // (six shifts: every wave evaluates two of them in turn).  A restart occupies a CU for the whole run, so this is the path of
-    // the SMALL runs (BASELINE.json configs[3]: 256 restarts): measured against the step-by-step path below, us per update,
-    // three shifts: R = 256: 19.9 / 34, 512: 40.8 / 45.4, 1 024: 77 / 63, 21 845: 1 552 / 785; six shifts: R = 128: 40.6 / 35.6, 256: 41.0 / 44.1.
-    const bool d8_fused_pays = nsh == 3 ? R <= 512 : (R <= 256 && 6 * R > 1024);
-    if (c->D == 8 && (nsh == 3 || nsh == 6) && d8_fused_pays && c->default_solver == QMPS_ENV_DIRECT && (kind == QMPS_ANSATZ_SHALLOW_CNOT || kind == QMPS_ANSATZ_SHALLOW_CNOT3) &&
-        n_params <= 64 && documented_switch("QMPS_NO_FUSED_ROTO") == nullptr) {
-      qmps::RotoArgs ra;
-      memset(&ra, 0, sizeof(ra));
-      ra.base = d_base; ra.h = c->d_h; ra.hist = d_hist;
-      ra.R = (int)R; ra.P = n_params; ra.n_terms = c->n_terms; ra.n_sweeps = n_sweeps; ra.max_iter = max_iter;
-      ra.tol = tol; ra.direct = 1; ra.nsh = nsh; ra.rule = c->roto_rule;
-#ifdef QMPS_D8_PROFILE
-      auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-      const double h0 = now();
-#endif
-      HIP_TRY(qmps::launch_rotosolve_fused_d8(kind, ra, c->stream));
-#ifdef QMPS_D8_PROFILE
-      const double h1 = now();
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      const double h2 = now();
-#endif
-      HIP_TRY(qmps::launch_ansatz(c->D, kind, d_base, n_params, c->d_A, R, c->stream));
-      c->n_states = R; c->ans_have = false; c->tensors_valid = true;
-      if (int e = qmps_energy_launch(c, R, max_iter, tol, c->default_solver)) return e;
-      c->have_guess = saved_guess;
-      if (int e = download_results((size_t)R * n_sweeps + kHistExtra)) return e;
-#ifdef QMPS_D8_PROFILE
-      fprintf(stderr, "[d8 profile] launch call %.0f us, kernel until sync %.0f us, final evaluation + downloads %.0f us\n", h1 - h0, h2 - h1, now() - h2);
-#endif
-      return QMPS_OK;
-    }
-    // One parameter update = shift build -> ansatz -> environment + energy -> closed-form update.  The
-    // parameter index lives in HBM and is advanced by the update kernel, so the sequence is captured ONCE
-    // into a hipGraph and replayed n_params x n_sweeps times: the sweep is launch-bound at small R.
-    // D = 4 with the direct solver: shift build and ansatz happen INSIDE the energy kernel (evaluation nsh r + k builds
-    // the tensor of restart r with shift k on parameter *d_idx straight into LDS): two kernels per parameter update
-    const bool fused = c->default_solver == QMPS_ENV_DIRECT && fusable_ansatz(c, kind);
-    auto evaluate = [&](int shifts) -> int {      // shifts = nsh: the shifted batch;  0: the R base vectors
-      const int64_t n = shifts > 0 ? (int64_t)shifts * R : R;
-      if (fused) {
-        c->ans_have = true; c->ans_kind = kind; c->ans_P = n_params; c->ans_src = d_base; c->ans_i = d_idx; c->ans_nsh = shifts;
-        c->tensors_valid = false;
-      } else {
-        // shifted tensors straight from the base vectors (the shift build is folded into the ansatz kernel)
-        HIP_TRY(qmps::launch_ansatz_shifted(c->D, kind, d_base, n_params, c->d_A, n, shifts, d_idx, c->stream));
-        c->ans_have = false; c->tensors_valid = true;
-      }
-      c->n_states = n;
-      return qmps_energy_launch(c, n, max_iter, tol, c->default_solver);
-    };
-    auto one_update = [&](bool first_of_sweep) -> int {
-      if (int e = evaluate(nsh)) return e;
-      // the shift-0 row of a sweep's first batch is the evaluation of the vectors the PREVIOUS sweep left: its record
-      if (first_of_sweep) HIP_TRY(qmps::launch_roto_record(c->d_E, d_hist, (int)R, c->n_terms, d_idx + 2, nsh, c->stream));
-      HIP_TRY(qmps::launch_roto_update(d_base, c->d_E, c->d_status, (int)R, n_params, d_idx, c->n_terms, nsh, c->roto_rule, c->stream));
-      return QMPS_OK;
-    };
-    // One sweep = n_params updates (the first one also records the previous sweep from its shift-0 rows).  The parameter index and the
-    // sweep counter live in HBM and are advanced by the update kernel, so the sweep is captured ONCE into a hipGraph and
-    // replayed n_sweeps times (a graph launch costs ~15 us: per update it was a third of the time, per sweep it is noise)
-    auto one_sweep = [&]() -> int {
-      for (int i = 0; i < n_params; ++i)
-        if (int e = one_update(i == 0)) return e;
-      return QMPS_OK;
-    };
-    const bool use_graph = documented_switch("QMPS_NO_GRAPH") == nullptr && n_params <= 256;
-    if (use_graph) {
-      qmps_ctx::RotoKey key;
-      key.R = R; key.kind = kind; key.P = n_params; key.nsh = nsh; key.max_iter = max_iter; key.n_terms = c->n_terms;
-      key.solver = c->default_solver; key.handoff = c->handoff; key.rule = c->roto_rule; key.tol = tol; key.fused = fused;
-      key.base = d_base; key.hist = d_hist; key.params = c->d_params; key.E = c->d_E;
-      if (!(c->roto_exec && key == c->roto_key)) {
-        if (c->roto_exec) (void)hipGraphExecDestroy(c->roto_exec);
-        if (c->roto_graph) (void)hipGraphDestroy(c->roto_graph);
-        c->roto_exec = nullptr; c->roto_graph = nullptr;
-        c->capturing = true;
-        HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        const int e = one_sweep();
-        const hipError_t ce = hipStreamEndCapture(c->stream, &c->roto_graph);
-        c->capturing = false;
-        if (e) return e;
-        HIP_TRY(ce);
-        HIP_TRY(hipGraphInstantiate(&c->roto_exec, c->roto_graph, nullptr, nullptr, 0));
-        c->roto_key = key;
-      }
-    }
-    for (int sw = 0; sw < n_sweeps; ++sw) {
-      if (use_graph) HIP_TRY(hipGraphLaunch(c->roto_exec, c->stream));
-      else if (int e = one_sweep()) return e;
-    }
-    // the last sweep's record, and the resident state the call leaves: one evaluation of the final vectors
-    if (int e = evaluate(0)) return e;
-    HIP_TRY(qmps::launch_roto_record(c->d_E, d_hist, (int)R, c->n_terms, d_idx + 2, 1, c->stream));
-    // The context's view of what is resident - a replayed graph runs no host code, so it is stated here, not inherited from
-    // the capture: the R final parameter vectors, their energies / statuses / environments
-    c->n_states = R;
-    c->window = 0;
-    c->have_env = true;
-    c->partials_B = -1;
-    c->acc_pending = false;
-    if (fused) {
-      // as a qmps_set_states_ansatz of the final parameters would leave it: rows resident in d_params, tensors on demand
-      HIP_TRY(hipMemcpyAsync(c->d_params, d_base, (size_t)R * n_params * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      c->ans_have = true; c->ans_kind = kind; c->ans_P = n_params; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
-      c->tensors_valid = false;
-    } else {
-      c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
-      c->tensors_valid = true;
-    }
-    c->have_guess = saved_guess;
-    return download_results((size_t)R * n_sweeps);
-  }();
-  c->capturing = false;
-  (void)hipStreamSynchronize(c->stream);
-  if (c->ans_src != nullptr) {     // an error left the context pointing at the run's own buffers
-    c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0; c->ans_have = false; c->tensors_valid = true; c->n_states = 0;
-  }
-  if (rc != QMPS_OK && c->roto_exec) {     // do not trust a sweep captured by a failed run
-    (void)hipGraphExecDestroy(c->roto_exec);
-    if (c->roto_graph) (void)hipGraphDestroy(c->roto_graph);
-    c->roto_exec = nullptr; c->roto_graph = nullptr;
-  }
-  return rc;
-}
-}  // namespace
 
 int qmps_get_states(qmps_ctx* c, int64_t B, double* A) try {
   if (int rc = bind(c)) return rc;

@@ -1,7 +1,7 @@
 // qmps_capi_evolve.hip - the evolve drivers of the C-ABI (declared in include/qmps_hip.h): the lock-step BFGS time evolution in one C call
 // (qmps_evolve_bfgs: host loop, or - D = 8, 16, round 5 - the optimiser algebra in kernels on device-resident state with the host
 // enqueueing chains of iterations; lock-step groups), the per-trajectory device-resident optimisers of D = 2, 4
-// (qmps_evolve_bfgs_device), the rotosolve time evolution (qmps_evolve_rotosolve), and the versioned option structs in front of them.
+// (qmps_evolve_bfgs_device), and the versioned option structs in front of them.  The rotosolve time evolution: qmps_capi_roto.hip.
 // Split out of qmps_capi_overlap.hip in round 5; the overlap launches they are built on: qmps_overlap_internal.h.
 #include "qmps_ctx.h"
 #include "qmps_overlap_internal.h"
@@ -824,128 +824,6 @@ int qmps_evolve_bfgs_device(qmps_ctx* c, int64_t T, int kind, int n_params, doub
   forget_resident_state(c);
   c->grad_warm_T = 0;
   return QMPS_OK;
-}
-QMPS_API_CATCH
-
-int qmps_evolve_rotosolve(qmps_ctx* c, int64_t T, int kind, int n_params, double* params, const double* WW, int n_steps,
-                          int n_sweeps, int nsh, int max_rounds, double tol, double* params_hist, double* f_hist) try {
-  if (int rc = bind(c)) return rc;
-  if (!params || !WW || !f_hist) return fail(QMPS_ERR_ARG, "null argument");
-  if (nsh != 3 && nsh != 6) return fail(QMPS_ERR_ARG, "nsh must be 3 (single-frequency) or 6 (double-frequency)");
-  if (T < 1 || nsh * T > c->max_batch) return fail(QMPS_ERR_ARG, "%d T = %lld candidates exceed max_batch = %lld", nsh, (long long)(nsh * T), (long long)c->max_batch);
-  if (n_steps < 1 || n_sweeps < 1) return fail(QMPS_ERR_ARG, "n_steps and n_sweeps must be >= 1");
-  if (int rc = check_ansatz(c, kind, n_params)) return rc;
-  const bool squaring = overlap_squares(c);
-  const int cap = squaring ? 60 : (1 << 24);
-  if (max_rounds < 1 || max_rounds > cap || !(tol > 0.0)) return fail(QMPS_ERR_ARG, "bad max_rounds / tol (D = %d: max_rounds in [1, %d])", c->D, cap);
-  const int P = n_params;
-  const int64_t n_rec = (int64_t)n_steps * n_sweeps;
-  auto grow = [&](double*& buf, size_t& have, size_t need) -> int {
-    if (need > have) {
-      if (buf) HIP_TRY(hipFree(buf));
-      buf = nullptr;
-      have = 0;
-      HIP_TRY(hipMalloc((void**)&buf, need));
-      have = need;
-    }
-    return QMPS_OK;
-  };
-  if (int rc = grow(c->roto_base, c->roto_base_bytes, (size_t)T * P * sizeof(double))) return rc;
-  if (int rc = grow(c->roto_hist, c->roto_hist_bytes, (size_t)T * n_rec * sizeof(double))) return rc;
-  if (!c->roto_idx) HIP_TRY(hipMalloc((void**)&c->roto_idx, 4 * sizeof(int)));
-  if (int rc = ensure_refs(c, T)) return rc;
-  if (int rc = ensure_E(c, c->n_terms > 0 ? c->n_terms : 1)) return rc;
-  if (int rc = ensure_overlap_outputs(c)) return rc;
-  if (int rc = ensure_scratch(c, (size_t)n_steps * T * P * sizeof(double))) return rc;    // parameter history
-  // fixed points of the power method (D = 8, 16), one set per parameter plus one for the unshifted evaluation of a sweep:
-  // the candidates of parameter i come back to the same slot in the next sweep and in the next time step - by then the
-  // parameters have moved by one sweep's updates, so the resident fixed point is the natural warm start
-  const bool warm = !squaring;
-  const size_t slot_bytes = (size_t)nsh * T * env_bytes(c);
-  if (warm) {
-    const size_t need = (size_t)(P + 1) * slot_bytes;
-    if (need > c->xwarm_bytes) {
-      if (c->d_xwarm) HIP_TRY(hipFree(c->d_xwarm));
-      c->d_xwarm = nullptr;
-      c->xwarm_bytes = 0;
-      HIP_TRY(hipMalloc(&c->d_xwarm, need));
-      c->xwarm_bytes = need;
-    }
-    HIP_TRY(hipMemsetAsync(c->d_xwarm, 0, need, c->stream));       // all zero = cold start
-  }
-  double *d_base = c->roto_base, *d_hist = c->roto_hist, *d_phist = (double*)c->d_scratch;
-  int* d_idx = c->roto_idx;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  int rc = [&]() -> int {
-    HIP_TRY(hipMemcpyAsync(d_base, params, (size_t)T * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const int idx0[4] = {0, 0, 0, P};      // parameter index, arrival counter, finished sweeps, slot of the unshifted evaluation
-    HIP_TRY(hipMemcpyAsync(d_idx, idx0, sizeof(idx0), hipMemcpyHostToDevice, c->stream));
-    if (int e = set_ww(c, WW)) return e;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->window = 0;
-    forget_resident_state(c);
-    c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
-    auto evaluate = [&](int shifts) -> int {      // shifts = nsh: the shifted batch of parameter *d_idx;  0: the T base vectors
-      const int64_t n = shifts > 0 ? (int64_t)shifts * T : T;
-      HIP_TRY(qmps::launch_ansatz_shifted(c->D, kind, d_base, P, c->d_A, n, shifts, d_idx, c->stream));
-      qmps::OverlapArgs a;
-      memset(&a, 0, sizeof(a));
-      a.A = c->d_ref; a.Bt = c->d_A; a.WW = c->d_ww; a.eta = c->d_eta; a.f_out = c->d_E;
-      a.iters = c->d_iters; a.status = c->d_status; a.B = n; a.group = shifts > 0 ? shifts : 1;
-      a.max_rounds = max_rounds; a.tol = tol; a.stats = c->d_ostats;
-      if (warm) {
-        a.x_in = c->d_xwarm; a.r_out = c->d_xwarm;
-        a.slot_ptr = shifts > 0 ? d_idx : d_idx + 3; a.slot_stride = (int64_t)slot_bytes;
-      }
-      return launch_overlap_kernels(c, a);
-    };
-    auto one_sweep = [&]() -> int {
-      for (int i = 0; i < P; ++i) {
-        if (int e = evaluate(nsh)) return e;
-        HIP_TRY(qmps::launch_roto_update(d_base, c->d_E, c->d_status, (int)T, P, d_idx, 1, nsh, c->roto_rule, c->stream));
-      }
-      // the sweep's record: the objective of the updated vectors against this time step's reference states
-      if (int e = evaluate(0)) return e;
-      HIP_TRY(qmps::launch_roto_record(c->d_E, d_hist, (int)T, 1, d_idx + 2, 1, c->stream));
-      return QMPS_OK;
-    };
-    const bool use_graph = documented_switch("QMPS_NO_GRAPH") == nullptr && P <= 256;
-    if (use_graph) {
-      c->capturing = true;
-      HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-      const int e = one_sweep();
-      const hipError_t ce = hipStreamEndCapture(c->stream, &graph);
-      c->capturing = false;
-      if (e) return e;
-      HIP_TRY(ce);
-      HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    }
-    for (int step = 0; step < n_steps; ++step) {
-      // the states the step starts from are the reference: A_t = tensor(params_t)  (new_time_evolve.py:281-283)
-      HIP_TRY(qmps::launch_ansatz(c->D, kind, d_base, P, c->d_ref, T, c->stream));
-      for (int sw = 0; sw < n_sweeps; ++sw) {
-        if (use_graph) HIP_TRY(hipGraphLaunch(exec, c->stream));
-        else if (int e = one_sweep()) return e;
-      }
-      HIP_TRY(hipMemcpyAsync(d_phist + (size_t)step * T * P, d_base, (size_t)T * P * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(params, d_base, (size_t)T * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(f_hist, d_hist, (size_t)T * n_rec * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (params_hist) HIP_TRY(hipMemcpyAsync(params_hist, d_phist, (size_t)n_steps * T * P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return QMPS_OK;
-  }();
-  c->capturing = false;
-  (void)hipStreamSynchronize(c->stream);
-  if (exec) (void)hipGraphExecDestroy(exec);
-  if (graph) (void)hipGraphDestroy(graph);
-  // what the call leaves resident: the T final candidates (tensors, eta, objective, status) against the last step's references
-  c->n_states = rc == QMPS_OK ? T : 0;
-  c->tensors_valid = true;
-  c->overlap_refs = rc == QMPS_OK ? T : 0;
-  c->overlap_group = 0;
-  return rc;
 }
 QMPS_API_CATCH
 

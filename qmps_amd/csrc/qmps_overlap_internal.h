@@ -1,5 +1,5 @@
-// qmps_overlap_internal.h - helpers of the overlap entry points (qmps_capi_overlap.hip) that the evolve drivers (qmps_capi_evolve.hip)
-// build on.  Host side, library-internal.
+// qmps_overlap_internal.h - helpers of the overlap entry points (qmps_capi_overlap.hip) that the evolve drivers (qmps_capi_evolve.hip,
+// qmps_capi_roto.hip) build on.  Host side, library-internal.
 #pragma once
 #include "qmps_ctx.h"
 

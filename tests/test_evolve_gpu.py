@@ -192,6 +192,27 @@ def test_device_time_evolution_by_rotosolve_vs_oracle_replay(D, kind, P, T, n_st
     # so this driver is checked for what it computes; the optimiser that does the physics is method='BFGS' below)
 
 
+@pytest.mark.parametrize('D', [2, 4])
+def test_rotosolve_evolution_plain_launches_match_the_graph(D, engine_factory, monkeypatch):
+    """QMPS_NO_GRAPH: qmps_evolve_rotosolve enqueues every sweep's kernels itself instead of replaying the captured sweep - the
+    same kernels in the same order with the same arguments: the same numbers bit for bit, the same count of evaluations."""
+    _, kind, P, T, _, _, _, seed = min((case for case in ROTO_CASES if case[0] == D and case[6] == 3), key=lambda case: case[3])
+    X0 = np.random.default_rng(seed).standard_normal((T, P))
+    WW = WW_of(0.05)
+    eng = engine_factory(D, 4096)
+    runs = []
+    for no_graph in (False, True):
+        if no_graph:
+            monkeypatch.setenv('QMPS_NO_GRAPH', '1')
+        eng.overlap_stats(reset=True)
+        out = eng.evolve_rotosolve(kind, X0, WW, n_steps=2, n_sweeps=2, max_rounds=60, tol=1e-12)
+        monkeypatch.delenv('QMPS_NO_GRAPH', raising=False)
+        runs.append((out, eng.overlap_stats()['evaluations']))
+    (graph, n_graph), (plain, n_plain) = runs
+    assert all(np.array_equal(a, b) for a, b in zip(graph, plain))        # Xf, ph, fh
+    assert n_graph == n_plain == 2 * 2 * (3 * P + 1) * T
+
+
 def test_rotosolve_evolution_d16_above_the_queue_threshold(engine_factory):
     """at D = 16 a sweep of more than 2 048 candidates (nsh T > 2 048) runs the four-wave kernel with its
     work queue INSIDE the captured sweep graph - the queue counter must exist before the capture starts (it used to be

@@ -243,6 +243,34 @@ def test_cached_sweep_graph_is_replayed_faithfully(engine_factory):
             assert abs(h3[-1][b] - O.energy_closed_form(O.unitary_to_tensor(O.shallow_cnot_unitary(D, p3[b])[None])[0], h)) < 1e-9
 
 
+@pytest.mark.parametrize('D,P,double', [(2, 8, False), (4, 4, False), (4, 4, True)])
+def test_plain_launches_match_the_captured_sweep(D, P, double, engine_factory, monkeypatch):
+    """QMPS_NO_GRAPH: the step-by-step path enqueues every sweep's kernels itself instead of replaying the captured sweep - the
+    same kernels in the same order with the same arguments, so the run and the resident state it leaves are the same bit for
+    bit; and the cached graph survives a plain run in between."""
+    from qmps_amd import _lib
+    rng = np.random.default_rng(78)
+    R = 40
+    eng = engine_factory(D, 1024)
+    eng.set_hamiltonian(O.hamiltonian_matrix({'ZZ': -1, 'X': 1}))
+    run = eng.double_rotosolve if double else eng.rotosolve
+    P0 = rng.standard_normal((R, P))
+    monkeypatch.setenv('QMPS_NO_FUSED_ROTO', '1')       # (D = 2 would take the whole-run kernel)
+    runs = []
+    for plain in (False, True, False):
+        if plain:
+            monkeypatch.setenv('QMPS_NO_GRAPH', '1')
+        hist, p = run(_lib.ANSATZ_SHALLOW_CNOT, P0, 3)
+        monkeypatch.delenv('QMPS_NO_GRAPH', raising=False)
+        runs.append((hist, p, eng.results(R), eng.tensors(R)))
+    monkeypatch.delenv('QMPS_NO_FUSED_ROTO', raising=False)
+    h_graph, p_graph, res_graph, A_graph = runs[0]
+    for h_other, p_other, res_other, A_other in runs[1:]:
+        assert np.array_equal(h_graph, h_other, equal_nan=True) and np.array_equal(p_graph, p_other)
+        assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(res_graph, res_other))
+        assert np.array_equal(A_graph, A_other)
+
+
 @pytest.mark.parametrize('double', [False, True])
 def test_d2_whole_run_kernel_matches_the_step_by_step_path(double, engine_factory, monkeypatch):
     """D = 2: every sweep of every restart runs inside ONE kernel launch (single- and double-frequency); the same run through
