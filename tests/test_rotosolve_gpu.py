@@ -11,6 +11,7 @@ and directly only where the two runs stay within 1e-7 of each other)."""
 import numpy as np
 import pytest
 
+import operator_cases as OP
 from oracle import qmps_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -271,22 +272,16 @@ def test_plain_launches_match_the_captured_sweep(D, P, double, engine_factory, m
         assert np.array_equal(A_graph, A_other)
 
 
-@pytest.mark.parametrize('double', [False, True])
-def test_d2_whole_run_kernel_matches_the_step_by_step_path(double, engine_factory, monkeypatch):
-    """D = 2: every sweep of every restart runs inside ONE kernel launch (single- and double-frequency); the same run through
-    the step-by-step path (ansatz / energy / update kernels per parameter) gives the same trajectories."""
+def d2_whole_run_against_step_by_step(double, h, runs, sweeps, eng, monkeypatch, c_oracle=None):
+    """runs: (kind, start vectors) in turn.  With `c_oracle` also the C oracle's energy at every final parameter vector."""
     from qmps_amd import _lib
-    rng = np.random.default_rng(123)
-    h = np.stack([O.hamiltonian_matrix({'ZZ': -1, 'X': 1}), O.hamiltonian_matrix({'XX': 1, 'YY': 1, 'ZZ': 0.5})])
-    eng = engine_factory(2, 4096)
     eng.set_hamiltonian(h)
     run = eng.double_rotosolve if double else eng.rotosolve
-    for kind, P in ((_lib.ANSATZ_SHALLOW_CNOT, 8), (_lib.ANSATZ_SHALLOW_QAOA, 4), (_lib.ANSATZ_SHALLOW_FULL, 15)):
-        P0 = rng.standard_normal((50, P))
+    for kind, P0 in runs:
         monkeypatch.delenv('QMPS_NO_FUSED_ROTO', raising=False)
-        h1, p1 = run(kind, P0, 3)
+        h1, p1 = run(kind, P0, sweeps)
         monkeypatch.setenv('QMPS_NO_FUSED_ROTO', '1')
-        h2, p2 = run(kind, P0, 3)
+        h2, p2 = run(kind, P0, sweeps)
         monkeypatch.delenv('QMPS_NO_FUSED_ROTO', raising=False)
         both = ~(np.isnan(h1).any(0) | np.isnan(h2).any(0))
         assert both.mean() > 0.8
@@ -303,28 +298,47 @@ def test_d2_whole_run_kernel_matches_the_step_by_step_path(double, engine_factor
             for b in np.flatnonzero(both)[::7]:
                 Ab = O.unitary_to_tensor(build(2, p1[b])[None])[0]
                 assert abs(h1[-1][b] - sum(O.energy_closed_form(Ab, h[t]) for t in range(2))) < 1e-9
+        if c_oracle is not None:
+            e_at_p, st_at_p = oracle_energies(c_oracle, OP.ROTO_BUILDERS[kind], 2, p1, h)
+            ok = both & (st_at_p == 0)
+            print(f'whole-run rotosolve D = 2, kind {kind}, {"six" if double else "three"} shifts: max |E - C oracle at the final parameters| = '
+                  f'{np.abs(e_at_p - h1[-1])[ok].max():.2e} on {int(ok.sum())} of {len(p1)} restarts')
+            assert ok.any() and np.abs(e_at_p - h1[-1])[ok].max() < 1e-9
 
 
 @pytest.mark.parametrize('double', [False, True])
-def test_d8_whole_run_kernel_matches_the_step_by_step_path(double, c_oracle, engine_factory, monkeypatch):
-    """D = 8 (ShallowCNOT families): a workgroup per restart, a wave per shift, every sweep inside ONE launch - with the state
-    tensor built by the wave-distributed circuit (butterflies across lanes) - against the step-by-step path (ansatz / solve +
-    energy / update kernels per parameter) and against the oracle at the final parameters."""
+def test_d2_whole_run_kernel_matches_the_step_by_step_path(double, engine_factory, monkeypatch):
+    """D = 2: every sweep of every restart runs inside ONE kernel launch (single- and double-frequency); the same run through
+    the step-by-step path (ansatz / energy / update kernels per parameter) gives the same trajectories."""
     from qmps_amd import _lib
-    rng = np.random.default_rng(888)
-    h = np.stack([O.hamiltonian_matrix({'XX': 1, 'YY': 1, 'ZZ': 0.5}), 0.3 * O.hamiltonian_matrix({'ZZ': -1, 'X': 1})])
-    eng = engine_factory(8, 4096)
+    rng = np.random.default_rng(123)
+    h = np.stack([O.hamiltonian_matrix({'ZZ': -1, 'X': 1}), O.hamiltonian_matrix({'XX': 1, 'YY': 1, 'ZZ': 0.5})])
+    runs = [(kind, rng.standard_normal((50, P))) for kind, P in ((_lib.ANSATZ_SHALLOW_CNOT, 8), (_lib.ANSATZ_SHALLOW_QAOA, 4), (_lib.ANSATZ_SHALLOW_FULL, 15))]
+    d2_whole_run_against_step_by_step(double, h, runs, 3, engine_factory(2, 4096), monkeypatch)
+
+
+@pytest.mark.parametrize('double', [False, True])
+def test_d2_whole_run_kernel_with_a_generic_hamiltonian_term(double, c_oracle, engine_factory, monkeypatch):
+    """rotosolve_fused_d2_kernel evaluates its energies in its own code, which had seen TFIM and XXZ only - real symmetric terms,
+    invariant under exchanging the sites.  Here h stacks TFIM and a complex Hermitian term with neither symmetry
+    (operator_cases.roto_hamiltonian; tests/test_operator_cases_cpu.py: h -> h^T moves the energies of these start vectors by 4e-3
+    at least, h -> S h S not at all - D = 2 is blind to the order of the sites).  16 restarts, 2 sweeps; every assertion of the test
+    above, and the C oracle's energy at every final parameter vector to 1e-9."""
+    runs = [(kind, OP.roto_start(2, kind, P, 16)) for kind, P in OP.ROTO_RUNS[2]]
+    d2_whole_run_against_step_by_step(double, OP.roto_hamiltonian(2), runs, 2, engine_factory(2, 4096), monkeypatch, c_oracle)
+
+
+def d8_whole_run_against_step_by_step(double, h, runs, sweeps, c_oracle, eng, monkeypatch, what=None):
+    """runs: (kind, builder, start vectors) in turn"""
     eng.set_hamiltonian(h)
     run = eng.double_rotosolve if double else eng.rotosolve
-    for kind, P, builder in ((_lib.ANSATZ_SHALLOW_CNOT, 6, O.shallow_cnot_unitary), (_lib.ANSATZ_SHALLOW_CNOT3, 9, O.shallow_cnot3_unitary),
-                             (_lib.ANSATZ_SHALLOW_CNOT, 8, O.shallow_cnot_unitary)):      # (fewer than three layers: no full-rank environment at D = 8)
-        R = 180 if double else 40          # (six shifts: the whole-run kernel serves 1 024 < 6 R <= 1 536 evaluations per update)
-        P0 = rng.standard_normal((R, P))
+    for kind, builder, P0 in runs:
+        R = len(P0)
         monkeypatch.delenv('QMPS_NO_FUSED_ROTO', raising=False)
-        h1, p1 = run(kind, P0, 3)
+        h1, p1 = run(kind, P0, sweeps)
         E1 = eng.results(R)[0].sum(1)                    # the resident state the call leaves: energies of the final vectors
         monkeypatch.setenv('QMPS_NO_FUSED_ROTO', '1')
-        h2, p2 = run(kind, P0, 3)
+        h2, p2 = run(kind, P0, sweeps)
         monkeypatch.delenv('QMPS_NO_FUSED_ROTO', raising=False)
         both = ~(np.isnan(h1).any(0) | np.isnan(h2).any(0))
         assert both.mean() > 0.8
@@ -339,7 +353,38 @@ def test_d8_whole_run_kernel_matches_the_step_by_step_path(double, c_oracle, eng
         assert np.abs(E1 - h1[-1])[both].max() < 1e-10
         e_at_p, st_at_p = oracle_energies(c_oracle, builder, 8, p1, h)
         ok = both & (st_at_p == 0)
+        if what:
+            print(f'{what}, kind {kind} P {P0.shape[1]}, {"six" if double else "three"} shifts: max |E - C oracle at the final parameters| = '
+                  f'{np.abs(e_at_p - h1[-1])[ok].max():.2e} on {int(ok.sum())} of {R} restarts')
         assert np.abs(e_at_p - h1[-1])[ok].max() < 1e-9
+
+
+@pytest.mark.parametrize('double', [False, True])
+def test_d8_whole_run_kernel_matches_the_step_by_step_path(double, c_oracle, engine_factory, monkeypatch):
+    """D = 8 (ShallowCNOT families): a workgroup per restart, a wave per shift, every sweep inside ONE launch - with the state
+    tensor built by the wave-distributed circuit (butterflies across lanes) - against the step-by-step path (ansatz / solve +
+    energy / update kernels per parameter) and against the oracle at the final parameters."""
+    from qmps_amd import _lib
+    rng = np.random.default_rng(888)
+    h = np.stack([O.hamiltonian_matrix({'XX': 1, 'YY': 1, 'ZZ': 0.5}), 0.3 * O.hamiltonian_matrix({'ZZ': -1, 'X': 1})])
+    R = 180 if double else 40          # (six shifts: the whole-run kernel serves 1 024 < 6 R <= 1 536 evaluations per update)
+    runs = [(kind, builder, rng.standard_normal((R, P))) for kind, P, builder in
+            ((_lib.ANSATZ_SHALLOW_CNOT, 6, O.shallow_cnot_unitary), (_lib.ANSATZ_SHALLOW_CNOT3, 9, O.shallow_cnot3_unitary),
+             (_lib.ANSATZ_SHALLOW_CNOT, 8, O.shallow_cnot_unitary))]      # (fewer than three layers: no full-rank environment at D = 8)
+    d8_whole_run_against_step_by_step(double, h, runs, 3, c_oracle, engine_factory(8, 4096), monkeypatch)
+
+
+@pytest.mark.parametrize('double', [False, True])
+def test_d8_whole_run_kernel_with_a_generic_hamiltonian_term(double, c_oracle, engine_factory, monkeypatch):
+    """rotosolve_fused_d8_kernel keeps the Hamiltonian in LDS and takes its energies through the merged two-site tensor, in code that
+    had seen TFIM and XXZ only.  Here h stacks a complex Hermitian term that is neither symmetric nor invariant under exchanging
+    the sites and 0.3 TFIM (operator_cases.roto_hamiltonian; tests/test_operator_cases_cpu.py: h -> h^T and h -> S h S move the
+    energies of these start vectors by 1e-5 at least).  Three shifts: 16 restarts; six shifts: 176, the fewest for which the driver
+    takes the whole-run kernel (6 R > 1 024: qmps_capi_roto.hip) - with 16 the test would compare the step-by-step path with
+    itself.  2 sweeps; every assertion of the test above, the C oracle's energy at the final parameters among them (1e-9)."""
+    R = 176 if double else 16
+    runs = [(kind, OP.ROTO_BUILDERS[kind], OP.roto_start(8, kind, P, R)) for kind, P in OP.ROTO_RUNS[8]]
+    d8_whole_run_against_step_by_step(double, OP.roto_hamiltonian(8), runs, 2, c_oracle, engine_factory(8, 4096), monkeypatch, 'whole-run rotosolve D = 8')
 
 
 def test_config1_family_with_a_landscape_reaches_the_d2_optimum(c_oracle, engine_factory):
