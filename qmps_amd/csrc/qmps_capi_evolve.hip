@@ -2,7 +2,8 @@
 // (qmps_evolve_bfgs: host loop, or - D = 8, 16, round 5 - the optimiser algebra in kernels on device-resident state with the host
 // enqueueing chains of iterations; lock-step groups), the per-trajectory device-resident optimisers of D = 2, 4
 // (qmps_evolve_bfgs_device), and the versioned option structs in front of them.  The rotosolve time evolution: qmps_capi_roto.hip.
-// Split out of qmps_capi_overlap.hip in round 5; the overlap launches they are built on: qmps_overlap_internal.h.
+// The overlap objective and gradient they are built on: qmps_capi_overlap.hip (through qmps_overlap_internal.h); context + helpers:
+// qmps_capi.hip, qmps_ctx.h.
 #include "qmps_ctx.h"
 #include "qmps_overlap_internal.h"
 
@@ -826,29 +827,6 @@ int qmps_evolve_bfgs_device(qmps_ctx* c, int64_t T, int kind, int n_params, doub
   return QMPS_OK;
 }
 QMPS_API_CATCH
-
-int qmps_overlap_batch(qmps_ctx* c, int64_t B, const double* A, int a_shared, const double* states, int kind,
-                       int n_params, const double* WW, int max_rounds, double tol, double* eta_out, double* r_out,
-                       int32_t* rounds_out, int32_t* status_out) try {
-  if (int rc = bind(c)) return rc;
-  if (int rc = check_B(c, B)) return rc;
-  if (!A || !WW || !eta_out || (!states && B > 0)) return fail(QMPS_ERR_ARG, "null argument");
-  // candidates -> d_A: tensors, unitaries or ansatz parameters
-  if (kind == QMPS_INPUT_TENSOR || kind == QMPS_INPUT_UNITARY) {
-    if (int rc = qmps_set_states(c, B, states, kind)) return rc;
-  } else if (kind >= QMPS_INPUT_ANSATZ_BASE && kind <= QMPS_INPUT_ANSATZ_BASE + 6) {
-    if (int rc = qmps_set_states_ansatz(c, B, kind - QMPS_INPUT_ANSATZ_BASE, n_params, states)) return rc;
-  } else {
-    return fail(QMPS_ERR_ARG, "unknown input kind %d", kind);
-  }
-  if (B == 0) return QMPS_OK;
-  if (int rc = qmps_overlap_set(c, a_shared ? 1 : B, A, WW)) return rc;
-  if (int rc = qmps_overlap_launch(c, B, max_rounds, tol, r_out != nullptr ? QMPS_OVERLAP_WANT_R : 0)) return rc;
-  return qmps_overlap_get(c, B, eta_out, r_out, rounds_out, status_out);
-}
-QMPS_API_CATCH
-
-// ---- brick-wall (new_tdvp) contractions -------------------------------------------------------
 
 // ---- the evolve drivers behind versioned option structs (include/qmps_hip.h) ------------------------------------------------------------
 namespace {

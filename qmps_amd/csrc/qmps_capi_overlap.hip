@@ -1,6 +1,7 @@
 // qmps_capi_overlap.hip - the C-ABI of the time-evolution overlap objective (declared in include/qmps_hip.h): resident references and
-// candidates, the batched objective and its two-sided gradient.  The evolve drivers built on them: qmps_capi_evolve.hip (round 5).
-// Split out of qmps_capi.hip in round 3; shared context + helpers: qmps_ctx.h, qmps_overlap_internal.h.
+// candidates, the batched objective (resident, or one-shot: qmps_overlap_batch) and its two-sided gradient.  The drivers built on
+// them: qmps_capi_evolve.hip (BFGS), qmps_capi_roto.hip (rotosolve).  The state setters and the context: qmps_capi.hip; shared
+// helpers: qmps_ctx.h, qmps_overlap_internal.h.
 #include "qmps_ctx.h"
 #include "qmps_overlap_internal.h"
 
@@ -276,6 +277,27 @@ int qmps_overlap_get_objective(qmps_ctx* c, int64_t B, double* f_out) try {
   HIP_TRY(hipMemcpyAsync(f_out, c->d_f + c->window, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return QMPS_OK;
+}
+QMPS_API_CATCH
+
+int qmps_overlap_batch(qmps_ctx* c, int64_t B, const double* A, int a_shared, const double* states, int kind,
+                       int n_params, const double* WW, int max_rounds, double tol, double* eta_out, double* r_out,
+                       int32_t* rounds_out, int32_t* status_out) try {
+  if (int rc = bind(c)) return rc;
+  if (int rc = check_B(c, B)) return rc;
+  if (!A || !WW || !eta_out || (!states && B > 0)) return fail(QMPS_ERR_ARG, "null argument");
+  // candidates -> d_A: tensors, unitaries or ansatz parameters
+  if (kind == QMPS_INPUT_TENSOR || kind == QMPS_INPUT_UNITARY) {
+    if (int rc = qmps_set_states(c, B, states, kind)) return rc;
+  } else if (kind >= QMPS_INPUT_ANSATZ_BASE && kind <= QMPS_INPUT_ANSATZ_BASE + 6) {
+    if (int rc = qmps_set_states_ansatz(c, B, kind - QMPS_INPUT_ANSATZ_BASE, n_params, states)) return rc;
+  } else {
+    return fail(QMPS_ERR_ARG, "unknown input kind %d", kind);
+  }
+  if (B == 0) return QMPS_OK;
+  if (int rc = qmps_overlap_set(c, a_shared ? 1 : B, A, WW)) return rc;
+  if (int rc = qmps_overlap_launch(c, B, max_rounds, tol, r_out != nullptr ? QMPS_OVERLAP_WANT_R : 0)) return rc;
+  return qmps_overlap_get(c, B, eta_out, r_out, rounds_out, status_out);
 }
 QMPS_API_CATCH
 

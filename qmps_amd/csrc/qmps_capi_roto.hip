@@ -1,6 +1,8 @@
 // qmps_capi_roto.hip - the rotosolve drivers of the C-ABI (declared in include/qmps_hip.h): qmps_rotosolve / qmps_double_rotosolve on the
 // energy (a function per path: the whole-run kernels of D = 2 and D = 8, the step-by-step path with its cached sweep graph) and
-// qmps_evolve_rotosolve on the time-evolution overlap objective, on the same work buffers and sweep-graph plumbing.
+// qmps_evolve_rotosolve on the time-evolution overlap objective, on the same work buffers and sweep-graph plumbing.  The launches they
+// enqueue: qmps_capi_energy.hip, qmps_capi_overlap.hip; the BFGS evolve drivers: qmps_capi_evolve.hip; context + helpers: qmps_capi.hip,
+// qmps_ctx.h.
 #include "qmps_ctx.h"
 #include "qmps_overlap_internal.h"
 

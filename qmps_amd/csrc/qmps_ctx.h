@@ -1,7 +1,13 @@
 // qmps_ctx.h - internal to libqmps_hip.so: the context behind the opaque `qmps_ctx*` of include/qmps_hip.h and the host-side
-// helpers shared by the translation units of the C-ABI (qmps_capi.hip: lifetime, states, energy path, exchange;
-// qmps_capi_overlap.hip: the time-evolution overlap objective and its gradient; qmps_capi_evolve.hip: the BFGS evolve drivers;
-// qmps_capi_roto.hip: the rotosolve drivers of the energy and of the overlap objective).
+// helpers shared by the translation units of the C-ABI:
+//   qmps_capi.hip            error string, context lifetime, states and settings, timers; defines the helpers declared below
+//   qmps_capi_energy.hip     the energy path, read-back, the one-shot batch calls, the two-site unit cell
+//   qmps_capi_cost.hip       the summed-cost exchange and its RCCL communicator (setup_accumulator, close_group)
+//   qmps_capi_brickwall.hip  the brick-wall calls
+//   qmps_capi_probe.hip      the peak probes
+//   qmps_capi_overlap.hip    the time-evolution overlap objective and its gradient
+//   qmps_capi_evolve.hip     the BFGS evolve drivers
+//   qmps_capi_roto.hip       the rotosolve drivers of the energy and of the overlap objective
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -288,5 +294,9 @@ bool fusable_ansatz(const qmps_ctx* c, int kind);
 int ensure_pinned(qmps_ctx* c, size_t bytes);
 int check_ansatz(const qmps_ctx* c, int kind, int n_params);
 int ensure_tensors(qmps_ctx* c);
+// the summed-cost exchange (qmps_capi_cost.hip): an accumulating energy launch claims the ring position of the following
+// qmps_cost_launch; the current group of summed costs goes out in one all-reduce
+int setup_accumulator(qmps_ctx* c, qmps::LaneArgs& a, int64_t B, int64_t adds, int per_add);
+int close_group(qmps_ctx* c);
 
 }  // namespace qmps_host

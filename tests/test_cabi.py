@@ -113,17 +113,22 @@ def test_nothing_throws_across_the_abi():
     for kind, word in ((1, b'out of host memory'), (2, b'exception'), (3, b'unknown C++ exception')):
         assert lib.qmps_selftest_exception(kind) == _lib.QMPS_ERR_ARG
         assert word in lib.qmps_last_error(), lib.qmps_last_error()
-    csrc = os.path.join(ROOT, 'qmps_amd', 'csrc')
-    for f in ('qmps_capi.hip', 'qmps_capi_overlap.hip', 'qmps_capi_evolve.hip', 'qmps_capi_roto.hip'):
-        src = open(os.path.join(csrc, f)).read()
+    import glob
+    files = sorted(glob.glob(os.path.join(ROOT, 'qmps_amd', 'csrc', 'qmps_capi*.hip')))     # every translation unit of the C-ABI
+    defined = set()
+    for f in files:
+        src = open(f).read()
         entry = re.findall(r'^int (qmps_\w+)\(', src, flags=re.M)
         guarded = re.findall(r'^int (qmps_\w+)\([^{;]*?\) try \{', src, flags=re.M | re.S)
         bare = sorted(set(entry) - set(guarded) - {'qmps_abi_version', 'qmps_abi_minor'})
         assert not bare, f'{f}: entry points without a function-try-block: {bare}'
         assert src.count('QMPS_API_CATCH') == len(guarded)
+        defined |= set(entry)
+    # ... and these files define exactly the bound entry points: none sits in a file the checks above do not read
+    assert defined == set(_lib.SIGNATURES) - {'qmps_last_error'}
     # context fields that are switched for the duration of a call are restored by scope guards, not by hand
-    for f in ('qmps_capi.hip', 'qmps_capi_overlap.hip', 'qmps_capi_evolve.hip', 'qmps_capi_roto.hip'):
-        src = open(os.path.join(csrc, f)).read()
+    for f in files:
+        src = open(f).read()
         assert 'c->defer_sync = true' not in src and 'saved_period' not in src and 'saved_guess' not in src
 
 
