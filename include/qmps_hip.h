@@ -39,7 +39,7 @@ extern "C" {
 #endif
 
 #define QMPS_ABI_VERSION 6
-#define QMPS_ABI_MINOR 6
+#define QMPS_ABI_MINOR 7
 
 /* error codes */
 #define QMPS_OK 0
@@ -191,7 +191,8 @@ int qmps_abi_version(void);
  * 6.6: qmps_overlap_gradient at a TIED iterate (D = 4): f_out is the solve's own common modulus with QMPS_OVERLAP_TWO_SIDED_F as well (the quotient of
  *      the two mixtures used to overwrite it), g_out is NaN (it was expanded round the mixtures), and status_out combines the two solves so that a
  *      status that is not usable beats QMPS_STATUS_TIED (a max let TIED hide NOT_CONVERGED).  qmps_evolve_bfgs at D = 4 eigen-solves the 2 n_params
- *      neighbours of its tied iterates one by one, as qmps_evolve_bfgs_device does. */
+ *      neighbours of its tied iterates one by one, as qmps_evolve_bfgs_device does.
+ * 6.7: qmps_ansatz_probe (the tensors of the device ansatz builders: plain, rotosolve-shifted and central-difference batches; test hook). */
 int qmps_abi_minor(void);
 const char* qmps_last_error(void);
 /* Test hook for the contract above ("nothing throws across the ABI"): raises a C++ exception inside the library - kind 1
@@ -280,6 +281,23 @@ int qmps_get_roto_rule(qmps_ctx* ctx, int* rule);
  * abcd[i][4] = (a, b, c, d).  Test / audit hook: lets a caller compare the device's decisions with scipy's
  * `minimize_scalar(f, bounds=[-pi, pi]).x` on the same fits (qmps/tools.py:451) without an energy landscape around them. */
 int qmps_roto_rule_probe(qmps_ctx* ctx, int64_t n, const double* abcd, int rule, double* theta);
+/* The device ansatz builders alone: A_out[B][2][D][D] complex128 = the tensors the builder kernels in front of every energy, rotosolve,
+ * gradient and evolve batch write.  Test / audit hook; it makes the same launch calls as the drivers.
+ *   nsh = 0, fd_h = 0:        plain build of params[B][n_params] (what qmps_set_states_ansatz builds);
+ *   nsh in {3, 6}, fd_h = 0:  rotosolve batch of params[B / nsh][n_params]: evaluation nsh r + k is row r with shift k of the drivers' tables
+ *                             ({0, +pi/2, -pi/2}; {0, pi, +-pi/2, +-pi/4}) added to parameter `index`, which is read from device memory as in
+ *                             the drivers;
+ *   fd_h != 0 (nsh = 0):      central-difference batch of params[B / (2 n_params)][n_params]: evaluation 2 n_params r + k is row r with +fd_h
+ *                             (k < n_params) or -fd_h added to parameter k mod n_params; `active` (nullable, one byte per row): rows with a
+ *                             zero byte are not built.
+ * fill (nullable): one complex value (re, im) written to every element of the output before the build, so that a caller sees which
+ * elements a masked build left untouched.  (kind, n_params) are checked as by qmps_set_states_ansatz; B must be a multiple of the
+ * evaluations per row and at most max_batch, index inside [0, n_params): QMPS_ERR_ARG otherwise.
+ * The build goes to scratch memory: the context's resident states, parameters and environments are NOT touched - a following
+ * qmps_get_states returns what it would have returned without the probe. */
+int qmps_ansatz_probe(qmps_ctx* ctx, int64_t B, int kind, int n_params, const double* params /* [rows][n_params] */, int nsh, int index,
+                      double fd_h, const unsigned char* active /* nullable, [rows] */, const double* fill /* nullable */,
+                      double* A_out /* [B][2][D][D] complex128 */);
 /* read back the resident state tensors A[B][2][D][D] (tests / debugging) */
 int qmps_get_states(qmps_ctx* ctx, int64_t B, double* A);
 /* h[n_terms][4][4] complex128, row/col index = 2*s1+s2, s1 = left site

@@ -103,6 +103,26 @@ class EnergyEngine:
         L.check(self._lib.qmps_roto_rule_probe(self._ctx, len(abcd), _f64(abcd), int(rule), _f64(out)))
         return out
 
+    def ansatz_probe(self, kind, params, nsh=0, index=0, fd_h=0.0, active=None, fill=None):
+        """The device ansatz builders alone (qmps_ansatz_probe): params (rows, P) -> tensors (B, 2, D, D).  nsh = 0, fd_h = 0: plain build,
+        B = rows; nsh in (3, 6): rotosolve batch, B = nsh rows, evaluation nsh r + k = row r with shift k on parameter `index`; fd_h != 0:
+        central-difference batch, B = 2 P rows, evaluation 2 P r + k = row r with +fd_h (k < P) or -fd_h on parameter k mod P, rows whose
+        `active` byte is 0 left unbuilt.  fill: complex value every output element holds before the build.  Resident states stay as they are."""
+        params = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float64)
+        rows, P = params.shape
+        B = rows * (2 * P if fd_h != 0.0 else (int(nsh) if nsh else 1))
+        mask = None
+        if active is not None:
+            mask = np.ascontiguousarray(active, dtype=np.uint8)
+            if mask.shape != (rows,):
+                raise ValueError(f'active: expected shape ({rows},), got {mask.shape}')
+            mask = mask.tobytes()
+        fl = None if fill is None else np.array([complex(fill).real, complex(fill).imag])
+        A = np.empty((B, 2, self.D, self.D), dtype=np.complex128)
+        L.check(self._lib.qmps_ansatz_probe(self._ctx, B, int(kind), P, _f64(params), int(nsh), int(index), float(fd_h), mask,
+                                            None if fl is None else _f64(fl), _f64(A.view(np.float64))))
+        return A
+
     def double_rotosolve(self, kind, params, n_sweeps=1, max_iter=10000, tol=1e-13, rule=L.ROTO_REFERENCE):
         """Device-resident DOUBLE-frequency rotosolve (qmps/tools.py:422-457): params (R, P) ->
         (energies (n_sweeps, R), params (R, P)); needs 6 R <= max_batch and a resident Hamiltonian.

@@ -25,6 +25,9 @@ def test_header_symbols_exported_and_bound():
     # the ctypes table binds exactly the declared entry points
     assert sorted(_lib.SIGNATURES) == names
     assert lib.qmps_abi_version() == 6 and lib.qmps_abi_minor() >= 1
+    # 6.7: the builder probe; the header's minor number is the library's
+    assert 'qmps_ansatz_probe' in names and lib.qmps_abi_minor() == 7
+    assert re.search(r'#define QMPS_ABI_MINOR 7\b', open(os.path.join(ROOT, 'include', 'qmps_hip.h')).read())
 
 
 def test_no_cpu_fallback_without_device():
