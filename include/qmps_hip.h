@@ -192,7 +192,8 @@ int qmps_abi_version(void);
  *      the two mixtures used to overwrite it), g_out is NaN (it was expanded round the mixtures), and status_out combines the two solves so that a
  *      status that is not usable beats QMPS_STATUS_TIED (a max let TIED hide NOT_CONVERGED).  qmps_evolve_bfgs at D = 4 eigen-solves the 2 n_params
  *      neighbours of its tied iterates one by one, as qmps_evolve_bfgs_device does.
- * 6.7: qmps_ansatz_probe (the tensors of the device ansatz builders: plain, rotosolve-shifted and central-difference batches; test hook). */
+ * 6.7: qmps_ansatz_probe (the tensors of the device ansatz builders: plain, rotosolve-shifted and central-difference batches; test hook).
+ *      Added later without a bump (detect it by the symbol's presence): qmps_correlators, the two-point functions of the resident states. */
 int qmps_abi_minor(void);
 const char* qmps_last_error(void);
 /* Test hook for the contract above ("nothing throws across the ABI"): raises a C++ exception inside the library - kind 1
@@ -345,6 +346,20 @@ int qmps_get_status(qmps_ctx* ctx, int64_t B, int32_t* status /* [B] */);
 int qmps_get_env(qmps_ctx* ctx, int64_t B, double* r);
 /* two-site reduced density matrix rho[B][4][4] complex128: rho[t][s] = tr(B_t r B_s^+)/tr r */
 int qmps_get_rdm(qmps_ctx* ctx, int64_t B, double* rho);
+/* Two-point functions of the resident states [window, window + B) with their resident environments (nothing is solved):
+ *   E_O(x) = sum_(t,s) O[t][s] A_s x A_t^+,   T(x) = sum_s A_s x A_s^+,   O[t][s] = <t|O|s> (the index order of h),
+ *   C_out[b][a][c][n-1] = tr(E_(O_a)(T^(n-1)(E_(O_c)(r)))) / tr r = <O_a(site 0) O_c(site n)>,  n = 1 .. n_max  (site 0 = the left site),
+ *   one_out[b][a]       = tr(E_(O_a)(r)) / tr r                   = <O_a>.
+ * ops: n_ops one-site operators, 2 x 2 complex, not necessarily Hermitian; 1 <= n_ops <= 4 (four span every one-site operator),
+ * 1 <= n_max <= 4096, and the result B * n_ops^2 * n_max * 16 bytes may not exceed 1 GiB (QMPS_ERR_ARG otherwise).  The left
+ * environment is taken to be the identity, as in qmps_get_rdm: for tensors that are not left isometries the formula above is still
+ * what is computed.  The status of the solve that produced r is not consulted (qmps_get_status); an evaluation whose tr r is zero or
+ * not finite yields NaN.  QMPS_ERR_STATE when no environment is resident (also after a launch with QMPS_FLAG_NO_ENV_OUT).
+ * One kernel launch; synchronous, with one synchronisation at the read-back.  Resident states, environments, energies, iteration
+ * counts and statuses stay exactly as they are. */
+int qmps_correlators(qmps_ctx* ctx, int64_t B, int n_ops, const double* ops /* [n_ops][2][2] complex128 */, int n_max,
+                     double* C_out   /* [B][n_ops][n_ops][n_max] complex128 */,
+                     double* one_out /* nullable, [B][n_ops] complex128 */);
 
 /* ---- one-shot host-buffer convenience (SURVEY 8(b) energy_batch / env_batch) ------------ */
 int qmps_energy_batch(qmps_ctx* ctx, int64_t B, const double* states, int kind, const double* h, int n_terms,

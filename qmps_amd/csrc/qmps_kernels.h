@@ -429,5 +429,16 @@ hipError_t launch_probe_copy(const void* src, void* dst, int64_t n16, hipStream_
 // copy of n8 x 8 bytes by a kernel on the given stream (pinned host memory <-> HBM without a copy-queue hop)
 hipError_t launch_stage_copy(const void* src, void* dst, int64_t n8, hipStream_t st);
 hipError_t launch_stage_copy2(const void* src1, void* dst1, int64_t n1, const void* src2, void* dst2, int64_t n2, hipStream_t st);
+// two-point functions of the resident states (qmps_correlator.hip): one launch for all n_ops^2 n_max values of every evaluation
+struct CorrelatorArgs {
+  const void* A;       // [B][2][D][D] complex
+  const void* r;       // [B][D][D] complex right environments (any normalisation: the results are divided by tr r)
+  const void* ops;     // [n_ops][2][2] complex, O[t][s] = <t|O|s> (device)
+  void* C;             // [B][n_ops][n_ops][n_max] complex: <O_a(site 0) O_c(site n)>, n = 1 .. n_max
+  void* one;           // nullable [B][n_ops] complex: <O_a>
+  int64_t B;
+  int n_ops, n_max;    // 1 <= n_ops <= 4, n_max >= 1
+};
+hipError_t launch_correlators(int D, const CorrelatorArgs& a, hipStream_t st);
 
 }  // namespace qmps

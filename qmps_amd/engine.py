@@ -254,6 +254,27 @@ class EnergyEngine:
         L.check(self._lib.qmps_get_rdm(self._ctx, B, _f64(rho.view(np.float64))))
         return rho
 
+    def correlators(self, ops, n_max, B=None, want_one_site=False):
+        """Two-point functions of the resident states with their resident environments (`launch` with the environments stored, or
+        `set_env_guess`; nothing is solved here): C[b, a, c, n - 1] = <O_a(site 0) O_c(site n)> for n = 1 .. n_max, shape
+        (B, m, m, n_max) complex128.  ops: (m, 2, 2) array-like or one (2, 2) matrix, O[t, s] = <t|O|s>, 1 <= m <= 4, need not be
+        Hermitian.  want_one_site=True: returns (C, one) with one[b, a] = <O_a>, shape (B, m).  One kernel launch, one synchronisation."""
+        B = self.B if B is None else int(B)
+        ops = np.asarray(ops, dtype=np.complex128)
+        if ops.shape == (2, 2):
+            ops = ops[None]
+        if ops.ndim != 3 or ops.shape[1:] != (2, 2):
+            raise ValueError(f'ops: expected shape (m, 2, 2) or (2, 2), got {ops.shape}')
+        ops = np.ascontiguousarray(ops)
+        m, n_max = ops.shape[0], int(n_max)
+        size = max(B, 0) * m * m * max(n_max, 0)
+        # (the library checks the sizes before anything is written: an array it refuses is never touched)
+        C = np.empty((B, m, m, n_max) if 0 <= size <= (1 << 26) else (0,), dtype=np.complex128)
+        one = np.empty((max(B, 0), m), dtype=np.complex128) if want_one_site else None
+        L.check(self._lib.qmps_correlators(self._ctx, B, m, _f64(ops.view(np.float64)), n_max, _f64(C.view(np.float64)),
+                                           None if one is None else _f64(one.view(np.float64))))
+        return (C, one) if want_one_site else C
+
     def summed_cost(self, B=None):
         cost = np.empty(max(self.n_terms, 1))
         L.check(self._lib.qmps_sum_energies(self._ctx, self.B if B is None else B, _f64(cost)))

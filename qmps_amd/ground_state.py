@@ -411,3 +411,29 @@ def ground_state_sweep(terms, coefficients, D=2, depth=2, state_tensor=ShallowCN
     if return_all:
         out['all_params'] = Xf
     return out
+
+
+def correlation_functions(params, ops, n_max, D=2, state_tensor=ShallowCNOTStateTensor, connected=False):
+    """Two-point functions of the states of K parameter rows - the companion of `ground_state_sweep` (params = out['params']):
+      C (K, m, m, n_max)   C[k, a, c, n - 1] = <O_a(site 0) O_c(site n)>, n = 1 .. n_max  (connected=True: minus <O_a> <O_c>)
+      one (K, m)           <O_a>
+      status (K,)          of the environment solve (STATUS_OK = 0; the correlators of any other row are not to be trusted)
+    ops: (m, 2, 2) one-site operators (or one (2, 2) matrix), m <= 4, not necessarily Hermitian.  The tensors are built on the device for
+    the ansatz classes libqmps_hip knows (`device_kind`), one environment solve runs with the environments stored, and ONE launch of the
+    correlator kernel walks the n_max transfer-map applications of every (state, operator) chain."""
+    P = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float64)
+    K = P.shape[0]
+    kind = getattr(state_tensor, 'device_kind', None)
+    on_device = kind is not None and not (kind in (2, 6) and D != 2)
+    eng = _runtime.engine(D, K)
+    if on_device:
+        eng.set_ansatz_params(kind, P)
+    else:
+        eng.set_unitaries(np.stack([unitary(build_gate(state_tensor, D, p_)) for p_ in P]))
+    eng.set_hamiltonian(np.zeros((1, 4, 4), dtype=np.complex128))      # the launch wants a resident Hamiltonian: a single zero term
+    eng.launch(K, max_iter=_GpuEnergyMixin.max_iter, tol=_GpuEnergyMixin.env_tol, solver='direct', store_env=True, krylov_fallback=D >= 8)
+    C, one = eng.correlators(ops, n_max, B=K, want_one_site=True)
+    status = eng.results_status(K)
+    if connected:
+        C = C - (one[:, :, None] * one[:, None, :])[..., None]
+    return C, one, status
