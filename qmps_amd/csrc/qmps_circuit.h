@@ -1,5 +1,5 @@
 // qmps_circuit.h - small-register circuit simulator and the ansatz gate lists (gfx950 only), shared by the kernel
-// translation units: ansatz_tensor_kernel / the rotosolve kernels (qmps_kernels.hip) and the fused D = 4 kernel, which
+// translation units: ansatz_tensor_kernel (qmps_ansatz.hip), the whole-run rotosolve kernel of D = 2 (qmps_energy_lane.hip) and the fused D = 4 kernel, which
 // builds the state tensor in front of the environment solve (qmps_direct.hip).  qmps/represent.py:268-404.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -10,20 +10,6 @@
 
 namespace qmps {
 
-template <int PATTERN>
-__device__ __forceinline__ double swz32(double v) {      // value of the lane (own index xor mask), within groups of 32 lanes
-  const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), PATTERN);
-  const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), PATTERN);
-  return __hiloint2double(hi, lo);
-}
-template <int PATTERN>
-__device__ __forceinline__ void rx_lanes(double& re, double& im, double c, double s) {      // a' = c a - i s (partner's a)
-  const double pr = swz32<PATTERN>(re), pi = swz32<PATTERN>(im);
-  const double nr = dfma(c, re, s * pi), ni = dfma(c, im, -s * pr);
-  re = nr;
-  im = ni;
-}
-
 // Column j (this lane's: j depends on the lane's half of the wave) of the five-qubit circuit: amplitude a = lane & 31 comes back in
 // (re, im).  cn / sn: cos / sin of HALF the angle l held by lane l of the wave (all 64 lanes call this together).
 // KIND 0: ShallowCNOTStateTensor (2 angles per layer), 3: ShallowCNOTStateTensor3 (3 angles per layer).

@@ -12,6 +12,7 @@
 
 #include "qmps_kernels.h"
 #include "qmps_device.h"
+#include "qmps_complex.h"
 
 namespace qmps {
 
@@ -19,23 +20,6 @@ namespace {
 
 constexpr int kMaxOps = 4;   // qmps_correlators refuses more: four operators span the one-site operators
 
-// acc += a b
-__device__ __forceinline__ void cfma(double2& acc, const double2 a, const double2 b) {
-  acc.x = dfma(a.x, b.x, acc.x);
-  acc.x = dfma(-a.y, b.y, acc.x);
-  acc.y = dfma(a.x, b.y, acc.y);
-  acc.y = dfma(a.y, b.x, acc.y);
-}
-// acc += a conj(b)
-__device__ __forceinline__ void cfma_conj(double2& acc, const double2 a, const double2 b) {
-  acc.x = dfma(a.x, b.x, acc.x);
-  acc.x = dfma(a.y, b.y, acc.x);
-  acc.y = dfma(a.y, b.x, acc.y);
-  acc.y = dfma(-a.x, b.y, acc.y);
-}
-__device__ __forceinline__ double2 cmul(const double2 a, const double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
 // 1 / t, NaN when t is zero or not finite (the documented answer of an evaluation without a usable environment)
 __device__ __forceinline__ double2 inv_trace(const double2 t) {
   const double s = fmax(fabs(t.x), fabs(t.y));
@@ -104,7 +88,7 @@ __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
         for (int s = 0; s < 2; ++s) {
           double2 m = make_double2(0.0, 0.0);
 #pragma unroll
-          for (int k = 0; k < D; ++k) cfma_conj(m, Acol[s][k], A[t][k][i]);
+          for (int k = 0; k < D; ++k) cfma_conj(Acol[s][k], A[t][k][i], m);
           M[t][s] = m;
         }
       for (int a = 0; a < n_ops; ++a) {
@@ -112,7 +96,7 @@ __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-          for (int s = 0; s < 2; ++s) cfma(l, O[a * 4 + t * 2 + s], M[t][s]);
+          for (int s = 0; s < 2; ++s) cfma(O[a * 4 + t * 2 + s], M[t][s], l);
         sL[a][i][lane] = l;
       }
     }
@@ -139,7 +123,7 @@ __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
       for (int l = 0; l < D; ++l) {
         double2 v = make_double2(0.0, 0.0);
 #pragma unroll
-        for (int k = 0; k < D; ++k) cfma_conj(v, x[k], A[t][l][k]);
+        for (int k = 0; k < D; ++k) cfma_conj(x[k], A[t][l][k], v);
         y[t][l] = v;
       }
   };
@@ -155,7 +139,7 @@ __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
 #pragma unroll
         for (int l = 0; l < D; ++l) {
           const double2 zz = make_double2(group_bcast<D, J>(z[s][l].x), group_bcast<D, J>(z[s][l].y));
-          cfma(out[l], arow, zz);
+          cfma(arow, zz, out[l]);
         }
       };
       row(std::integral_constant<int, 0>{});
@@ -170,7 +154,7 @@ __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
   auto read_out = [&](int a, const double2 (&x)[D]) {
     double2 v = make_double2(0.0, 0.0);
 #pragma unroll
-    for (int i = 0; i < D; ++i) cfma(v, sL[a][i][lane], x[i]);
+    for (int i = 0; i < D; ++i) cfma(sL[a][i][lane], x[i], v);
     return cmul(make_double2(group_sum<D>(v.x), group_sum<D>(v.y)), inv);
   };
 
@@ -196,9 +180,9 @@ __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
 #pragma unroll
       for (int l = 0; l < D; ++l) {
         z[0][l] = cmul(w00, y[0][l]);
-        cfma(z[0][l], w10, y[1][l]);
+        cfma(w10, y[1][l], z[0][l]);
         z[1][l] = cmul(w01, y[0][l]);
-        cfma(z[1][l], w11, y[1][l]);
+        cfma(w11, y[1][l], z[1][l]);
       }
     }
     left_mul(z, x);
@@ -285,7 +269,7 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
       for (int s = 0; s < 2; ++s) {
         double2 m = make_double2(0.0, 0.0);
 #pragma unroll
-        for (int k = 0; k < D; ++k) cfma_conj(m, sA[s][k][i], sA[t][k][j]);
+        for (int k = 0; k < D; ++k) cfma_conj(sA[s][k][i], sA[t][k][j], m);
         M[t][s] = m;
       }
 #pragma unroll
@@ -295,7 +279,7 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-          for (int s = 0; s < 2; ++s) cfma(l, O[a * 4 + t * 2 + s], M[t][s]);
+          for (int s = 0; s < 2; ++s) cfma(O[a * 4 + t * 2 + s], M[t][s], l);
       }
       Lji[a] = l;
     }
@@ -314,16 +298,16 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
 #pragma unroll
     for (int k = 0; k < D; ++k) {
       const double2 xc = sX[k][j];
-      cfma(y0, sA[0][i][k], xc);
-      cfma(y1, sA[1][i][k], xc);
+      cfma(sA[0][i][k], xc, y0);
+      cfma(sA[1][i][k], xc, y1);
     }
     if (identity) {
       sZ[0][i][j] = y0;
       sZ[1][i][j] = y1;
     } else {
       double2 z0 = cmul(w00, y0), z1 = cmul(w10, y0);
-      cfma(z0, w01, y1);
-      cfma(z1, w11, y1);
+      cfma(w01, y1, z0);
+      cfma(w11, y1, z1);
       sZ[0][i][j] = z0;
       sZ[1][i][j] = z1;
     }
@@ -332,7 +316,7 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int k = 0; k < D; ++k) cfma_conj(out, sZ[t][i][k], sA[t][j][k]);
+      for (int k = 0; k < D; ++k) cfma_conj(sZ[t][i][k], sA[t][j][k], out);
     return out;
   };
   // tr(L_a x) / tr r for every a, in every thread

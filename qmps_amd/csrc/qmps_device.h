@@ -79,6 +79,22 @@ __device__ __forceinline__ double quad_sum(double v) {
   v += quad_perm<0x4E>(v);   // [2,3,0,1]
   return v;
 }
+// ---- ds_swizzle butterflies (bit-mask mode: PATTERN = 0x1F | xor mask << 10) ----
+template <int PATTERN>
+__device__ __forceinline__ double swz32(double v) {      // value of the lane (own index xor mask), within groups of 32 lanes
+  const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), PATTERN);
+  const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), PATTERN);
+  return __hiloint2double(hi, lo);
+}
+// rx on the qubit whose bit is the lane-index bit selected by PATTERN, one amplitude (re, im) per lane
+template <int PATTERN>
+__device__ __forceinline__ void rx_lanes(double& re, double& im, double c, double s) {      // a' = c a - i s (partner's a)
+  const double pr = swz32<PATTERN>(re), pi = swz32<PATTERN>(im);
+  const double nr = dfma(c, re, s * pi), ni = dfma(c, im, -s * pr);
+  re = nr;
+  im = ni;
+}
+
 // v_rcp_f64 + one Newton step: relative error ~1e-16
 __device__ __forceinline__ double fast_rcp(double t) {
   const double x = __builtin_amdgcn_rcp(t);

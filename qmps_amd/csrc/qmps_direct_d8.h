@@ -1,5 +1,5 @@
 // qmps_direct_d8.h - the D = 8 direct fixed-point solve (gfx950 only) as a device function, shared by env_direct_d8_kernel
-// (qmps_direct.hip: writes the environments) and energy_block_kernel<8, true, FUSED> (qmps_kernels.hip: solve, acceptance step
+// (qmps_direct.hip: writes the environments) and energy_block_kernel<8, true, FUSED> (qmps_energy_block.hip: solve, acceptance step
 // and energies in ONE launch for the small batches of BASELINE.json configs[3]).  See env_direct_d8_kernel for the layout.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -8,6 +8,7 @@
 #include "qmps_kernels.h"
 #include "qmps_knobs.h"
 #include "qmps_device.h"
+#include "qmps_complex.h"
 
 namespace qmps {
 
@@ -27,26 +28,6 @@ namespace qmps {
 struct C4 {   // a complex matrix in C-layout: 4 registers re, 4 registers im
   v4f64 re, im;
 };
-
-// C += P * Q with P given in A-layout (pa_re/pa_im[kk]) and Q in B-layout (C-layout registers)
-__device__ __forceinline__ void cmma(const double (&pre)[4], const double (&pim)[4], const double (&pimn)[4],
-                                     const v4f64& qre, const v4f64& qim, v4f64& cre, v4f64& cim) {
-  // Three real products per k-slab instead of four (round 3, as in qmps_overlap.hip: K1 = (Pr + Pi) Qr, K2 = Pr (Qi - Qr),
-  // K3 = Pi (Qr + Qi); Re = K1 - K3, Im = K1 + K2): 12 v_mfma_f64_16x16x4 per complex product instead of 16, in three
-  // independent accumulator chains - the matrix pipe (~100 cycles per instruction on this part) bounds these kernels.
-  (void)pimn;
-  v4f64 k1 = {0, 0, 0, 0}, k2 = {0, 0, 0, 0}, k3 = {0, 0, 0, 0};
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const double ps = pre[kk] + pim[kk], qd = qim[kk] - qre[kk], qs = qre[kk] + qim[kk];
-    k1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ps, qre[kk], k1, 0, 0, 0);
-    k2 = __builtin_amdgcn_mfma_f64_16x16x4f64(pre[kk], qd, k2, 0, 0, 0);
-    k3 = __builtin_amdgcn_mfma_f64_16x16x4f64(pim[kk], qs, k3, 0, 0, 0);
-  }
-  cre += k1 - k3;
-  cim += k1 + k2;
-}
-
 
 template <bool SOLVE>
 __global__ __launch_bounds__(256) void energy_mfma_d16_kernel(LaneArgs p) {
@@ -105,13 +86,12 @@ __global__ __launch_bounds__(256) void energy_mfma_d16_kernel(LaneArgs p) {
       C4 n;
       n.re = (v4f64){0, 0, 0, 0};
       n.im = (v4f64){0, 0, 0, 0};
-      // A-layout of r = conj(C-layout): re as is, im negated; its negated imaginary part = + r.im
-      double rre[4], rimn[4], rim[4];
+      // A-layout of r = conj(C-layout): re as is, im negated
+      double rre[4], rim[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         rre[q] = r.re[q];
         rim[q] = -r.im[q];
-        rimn[q] = r.im[q];
       }
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
@@ -121,9 +101,9 @@ __global__ __launch_bounds__(256) void energy_mfma_d16_kernel(LaneArgs p) {
         y.im = (v4f64){0, 0, 0, 0};
         v4f64 bre = {are[s][0], are[s][1], are[s][2], are[s][3]};
         v4f64 bim = {aimn[s][0], aimn[s][1], aimn[s][2], aimn[s][3]};
-        cmma(rre, rim, rimn, bre, bim, y.re, y.im);
+        cmma16_3m(rre, rim, bre, bim, y.re, y.im);
         // r' += A_s Y
-        cmma(are[s], aim[s], aimn[s], y.re, y.im, n.re, n.im);
+        cmma16_3m(are[s], aim[s], y.re, y.im, n.re, n.im);
       }
       // hermitise through a padded LDS transpose, trace-normalise, compare
       __builtin_amdgcn_wave_barrier();
@@ -219,12 +199,11 @@ __global__ __launch_bounds__(256) void energy_mfma_d16_kernel(LaneArgs p) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) trp += (c == 4 * q + g) ? r.re[q] : 0.0;
     const double inv_tr = 1.0 / wave_sum(trp);
-    double rre[4], rimn[4], rim[4];
+    double rre[4], rim[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       rre[q] = r.re[q];
       rim[q] = -r.im[q];
-      rimn[q] = r.im[q];
     }
     __builtin_amdgcn_wave_barrier();      // sT is free again: rho[t][s] (wave-uniform) is parked in its first 16 slots
 #pragma unroll
@@ -234,19 +213,19 @@ __global__ __launch_bounds__(256) void energy_mfma_d16_kernel(LaneArgs p) {
       y.im = (v4f64){0, 0, 0, 0};
       v4f64 bre = {are[s2][0], are[s2][1], are[s2][2], are[s2][3]};
       v4f64 bim = {aimn[s2][0], aimn[s2][1], aimn[s2][2], aimn[s2][3]};
-      cmma(rre, rim, rimn, bre, bim, y.re, y.im);
+      cmma16_3m(rre, rim, bre, bim, y.re, y.im);
 #pragma unroll
       for (int t2 = 0; t2 < 2; ++t2) {
         C4 R;
         R.re = (v4f64){0, 0, 0, 0};
         R.im = (v4f64){0, 0, 0, 0};
-        cmma(are[t2], aim[t2], aimn[t2], y.re, y.im, R.re, R.im);
+        cmma16_3m(are[t2], aim[t2], y.re, y.im, R.re, R.im);
 #pragma unroll
         for (int t1 = 0; t1 < 2; ++t1) {
           C4 Z;
           Z.re = (v4f64){0, 0, 0, 0};
           Z.im = (v4f64){0, 0, 0, 0};
-          cmma(are[t1], aim[t1], aimn[t1], R.re, R.im, Z.re, Z.im);
+          cmma16_3m(are[t1], aim[t1], R.re, R.im, Z.re, Z.im);
 #pragma unroll
           for (int s1 = 0; s1 < 2; ++s1) {
             double pr = 0.0, pi = 0.0;
@@ -359,13 +338,12 @@ __global__ __launch_bounds__(128) void energy_mfma_d16x2_kernel(LaneArgs p) {
       C4 n;
       n.re = (v4f64){0, 0, 0, 0};
       n.im = (v4f64){0, 0, 0, 0};
-      // A-layout of r = conj(C-layout): re as is, im negated; its negated imaginary part = + r.im
-      double rre[4], rimn[4], rim[4];
+      // A-layout of r = conj(C-layout): re as is, im negated
+      double rre[4], rim[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         rre[q] = r.re[q];
         rim[q] = -r.im[q];
-        rimn[q] = r.im[q];
       }
       {
         // this wave's physical index s = wave:  Y = r A_s^+ (B operand = conj(A-layout of A_s) = (are, -aim)),  n_s = A_s Y
@@ -377,8 +355,8 @@ __global__ __launch_bounds__(128) void energy_mfma_d16x2_kernel(LaneArgs p) {
         part.im = (v4f64){0, 0, 0, 0};
         v4f64 bre = {are[s][0], are[s][1], are[s][2], are[s][3]};
         v4f64 bim = {aimn[s][0], aimn[s][1], aimn[s][2], aimn[s][3]};
-        cmma(rre, rim, rimn, bre, bim, y.re, y.im);
-        cmma(are[s], aim[s], aimn[s], y.re, y.im, part.re, part.im);
+        cmma16_3m(rre, rim, bre, bim, y.re, y.im);
+        cmma16_3m(are[s], aim[s], y.re, y.im, part.re, part.im);
         // r' = n_0 + n_1 through LDS, summed in the same order by both waves (bit-identical iterates, identical decisions)
 #pragma unroll
         for (int q = 0; q < 4; ++q) sX_all[wave][q * 64 + lane] = make_double2(part.re[q], part.im[q]);
@@ -487,12 +465,11 @@ __global__ __launch_bounds__(128) void energy_mfma_d16x2_kernel(LaneArgs p) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) trp += (c == 4 * q + g) ? r.re[q] : 0.0;
     const double inv_tr = 1.0 / wave_sum(trp);
-    double rre[4], rimn[4], rim[4];
+    double rre[4], rim[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       rre[q] = r.re[q];
       rim[q] = -r.im[q];
-      rimn[q] = r.im[q];
     }
     __builtin_amdgcn_wave_barrier();      // sT is free again: rho[t][s] (wave-uniform) is parked in its first 16 slots
     {
@@ -502,19 +479,19 @@ __global__ __launch_bounds__(128) void energy_mfma_d16x2_kernel(LaneArgs p) {
       y.im = (v4f64){0, 0, 0, 0};
       v4f64 bre = {are[s2][0], are[s2][1], are[s2][2], are[s2][3]};
       v4f64 bim = {aimn[s2][0], aimn[s2][1], aimn[s2][2], aimn[s2][3]};
-      cmma(rre, rim, rimn, bre, bim, y.re, y.im);
+      cmma16_3m(rre, rim, bre, bim, y.re, y.im);
 #pragma unroll
       for (int t2 = 0; t2 < 2; ++t2) {
         C4 R;
         R.re = (v4f64){0, 0, 0, 0};
         R.im = (v4f64){0, 0, 0, 0};
-        cmma(are[t2], aim[t2], aimn[t2], y.re, y.im, R.re, R.im);
+        cmma16_3m(are[t2], aim[t2], y.re, y.im, R.re, R.im);
 #pragma unroll
         for (int t1 = 0; t1 < 2; ++t1) {
           C4 Z;
           Z.re = (v4f64){0, 0, 0, 0};
           Z.im = (v4f64){0, 0, 0, 0};
-          cmma(are[t1], aim[t1], aimn[t1], R.re, R.im, Z.re, Z.im);
+          cmma16_3m(are[t1], aim[t1], R.re, R.im, Z.re, Z.im);
 #pragma unroll
           for (int s1 = 0; s1 < 2; ++s1) {
             double pr = 0.0, pi = 0.0;

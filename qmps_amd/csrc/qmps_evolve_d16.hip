@@ -34,7 +34,7 @@
 
 #include "qmps_kernels.h"
 #include "qmps_device.h"
-#include "qmps_overlap_d4.h"      // cmma16, cmma16_3m
+#include "qmps_complex.h"
 #include "qmps_circuit_wave.h"
 #include "qmps_evolve_core.h"
 

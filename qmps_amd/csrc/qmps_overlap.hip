@@ -8,7 +8,7 @@
 //
 // Power method in operator form (never builds the D^2 x D^2 matrix): x <- T(x)/||T(x)||_F from x_0 = 1/sqrt(D),
 // eta = <x, T x> (Rayleigh quotient, ||x||_F = 1), stop when ||T x - eta x||_F < tol.  status 1 = no unique dominant
-// eigenvalue within max_steps.  The D = 2 path (overlap_lane_kernel, qmps_kernels.hip) squares the 4 x 4 matrix instead.
+// eigenvalue within max_steps.  The D = 2 path (overlap_lane_kernel below, qmps_overlap_d2.h) squares the 4 x 4 matrix instead.
 //
 //   overlap_square_d4_kernel   D = 4: the map is ONE complex 16 x 16 tile - squared on the matrix cores until it is rank one
 //                              (O(log) rounds whatever the spectral gap), one wave per evaluation.

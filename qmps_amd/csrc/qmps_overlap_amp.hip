@@ -18,6 +18,7 @@
 namespace qmps {
 
 namespace {
+// (contracted expressions, not the four-FMA chains of cfma / cfma_conj in qmps_complex.h: replacing them changes the rounding)
 __device__ __forceinline__ double2 cmadd(double2 acc, double2 a, double2 b) {          // acc + a b
   return make_double2(acc.x + a.x * b.x - a.y * b.y, acc.y + a.x * b.y + a.y * b.x);
 }

@@ -1,66 +1,16 @@
 // qmps_overlap_d4.h - the D = 4 time-evolution overlap solve of ONE wave on the matrix cores (gfx950 only), shared by
-// overlap_square_d4_kernel (qmps_overlap.hip) and the device-resident BFGS time evolution (qmps_evolve_d4.hip); also the small complex
-// helpers and the complex 16 x 16 x 16 products on v_mfma_f64_16x16x4 of the overlap kernels.
+// overlap_square_d4_kernel (qmps_overlap.hip) and the device-resident BFGS time evolution (qmps_evolve_d4.hip).
 // Reference: qmps/new_time_evolve.py:193-221, scripts/loschmidt.py:209-239, qmps/time_evolve_tools.py:20-23.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "qmps_kernels.h"
 #include "qmps_device.h"
+#include "qmps_complex.h"
 
 namespace qmps {
 
 namespace {
-
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ void cfma(double2 a, double2 b, double2& c) {   // c += a b
-  c.x = dfma(a.x, b.x, c.x);
-  c.x = dfma(-a.y, b.y, c.x);
-  c.y = dfma(a.x, b.y, c.y);
-  c.y = dfma(a.y, b.x, c.y);
-}
-__device__ __forceinline__ void cfma_conj(double2 a, double2 b, double2& c) {   // c += a conj(b)
-  c.x = dfma(a.x, b.x, c.x);
-  c.x = dfma(a.y, b.y, c.x);
-  c.y = dfma(a.y, b.x, c.y);
-  c.y = dfma(-a.x, b.y, c.y);
-}
-
-}  // namespace
-
-namespace {
-
-// C += P * Q, P in A-layout (pre/pim[kk] = P[row = c][k = 4 kk + g]), Q in B-layout (qre/qim[kk] = Q[k = 4 kk + g][col = c])
-__device__ __forceinline__ void cmma16(const double (&pre)[4], const double (&pim)[4], const v4f64& qre, const v4f64& qim,
-                                       v4f64& cre, v4f64& cim) {
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    cre = __builtin_amdgcn_mfma_f64_16x16x4f64(pre[kk], qre[kk], cre, 0, 0, 0);
-    cim = __builtin_amdgcn_mfma_f64_16x16x4f64(pre[kk], qim[kk], cim, 0, 0, 0);
-    cre = __builtin_amdgcn_mfma_f64_16x16x4f64(-pim[kk], qim[kk], cre, 0, 0, 0);
-    cim = __builtin_amdgcn_mfma_f64_16x16x4f64(pim[kk], qre[kk], cim, 0, 0, 0);
-  }
-}
-
-// The same product with THREE real products per k-slab instead of four (K1 = (Pr + Pi) Qr, K2 = Pr (Qi - Qr), K3 = Pi (Qr + Qi);
-// Re = K1 - K3, Im = K1 + K2): 12 v_mfma_f64_16x16x4 per complex 16 x 16 x 16 product instead of 16, in three independent
-// accumulator chains of four.  The matrix pipe is what bounds the power iteration (a v_mfma_f64_16x16x4 occupies it for ~100
-// cycles on this part, profiles/EXPERIMENTS.md), the handful of extra additions run on the vector pipe beside it.  Rounding:
-// norm-wise the same bound as the four-product form (|error| <= c eps |P| |Q|).
-__device__ __forceinline__ void cmma16_3m(const double (&pre)[4], const double (&pim)[4], const v4f64& qre, const v4f64& qim,
-                                          v4f64& cre, v4f64& cim) {
-  v4f64 k1 = {0, 0, 0, 0}, k2 = {0, 0, 0, 0}, k3 = {0, 0, 0, 0};
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const double ps = pre[kk] + pim[kk], qd = qim[kk] - qre[kk], qs = qre[kk] + qim[kk];
-    k1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ps, qre[kk], k1, 0, 0, 0);
-    k2 = __builtin_amdgcn_mfma_f64_16x16x4f64(pre[kk], qd, k2, 0, 0, 0);
-    k3 = __builtin_amdgcn_mfma_f64_16x16x4f64(pim[kk], qs, k3, 0, 0, 0);
-  }
-  cre += k1 - k3;
-  cim += k1 + k2;
-}
-
 
 // The mixed transfer map of D = 4 IS one complex 16 x 16 tile, E[(i,i'),(j,j')] = sum_{s<4} C_s[i][j] conj(Bm_s[i'][j']); the power method
 // is taken 2^m steps at a time by SQUARING it (16 v_mfma_f64_16x16x4 per round, Frobenius-normalised) until it is rank one

@@ -20,19 +20,11 @@
 
 #include "qmps_kernels.h"
 #include "qmps_device.h"
-#include "qmps_overlap_d4.h"     // cmma16_3m
+#include "qmps_complex.h"
 
 namespace qmps {
 
 namespace {
-
-// (cfma: c += a b - qmps_overlap_d4.h)
-__device__ __forceinline__ void cfma_conj1(double2 a, double2 b, double2& c) {   // c += conj(a) b
-  c.x = dfma(a.x, b.x, c.x);
-  c.x = dfma(a.y, b.y, c.x);
-  c.y = dfma(a.x, b.y, c.y);
-  c.y = dfma(-a.y, b.x, c.y);
-}
 
 // sum of two values over the N = D * D threads of one item (consecutive lanes, or the whole workgroup at D = 16)
 template <int N>
@@ -127,7 +119,7 @@ __global__ __launch_bounds__((D * D < 64) ? 64 : D * D) void overlap_g_kernel(Ov
   for (int s = 0; s < 4; ++s) {
     double2 g = make_double2(0.0, 0.0);
 #pragma unroll
-    for (int k = 0; k < D; ++k) cfma_conj1(sYv[e][k][i], sC[e][s][k][j], g);
+    for (int k = 0; k < D; ++k) cfma_cj(sYv[e][k][i], sC[e][s][k][j], g);
     if (t < p.T && !(p.active != nullptr && p.active[t] == 0)) Gp[s * N + l] = g;
   }
   const double2 yv = sYv[e][i][j], rv = sR[e][i][j];
@@ -260,7 +252,7 @@ __global__ __launch_bounds__((D * D < 64) ? 64 : D * D) void overlap_probe_kerne
 }
 
 // D = 16: ONE WAVE per neighbour on the matrix cores (round 4).  merge(B', B')_s = B'_s1 B'_s2 are four complex 16 x 16 x 16 products:
-// 48 v_mfma_f64_16x16x4 in the three-product form (qmps_overlap_d4.h), operands loaded from HBM straight into the A- and
+// 48 v_mfma_f64_16x16x4 in the three-product form (qmps_complex.h), operands loaded from HBM straight into the A- and
 // B-layouts, the products left in the accumulator layout and contracted there with G_s (read in the same layout) - no LDS at all.
 // The round-3 kernel did the products on the vector pipe from an LDS copy (2 x 2 register tile per lane, 1 024 complex
 // multiply-adds per lane): 20.1 -> 18.4 us for the 4 352 probes of 256 iterates - the kernel is bound by the 35 MB of neighbour

@@ -30,6 +30,7 @@
 
 #include "qmps_kernels.h"
 #include "qmps_device.h"
+#include "qmps_complex.h"
 
 namespace qmps {
 
@@ -39,56 +40,6 @@ constexpr int KM = 16;          // basis size (one 16 x 16 tile for the projecte
 constexpr int KK = 5;           // Schur vectors kept at a restart (profiles/EXPERIMENTS.md: with FOUR a D = 16 candidate whose five largest eigenvalues lie within 2 % came back with the second one - its dominant direction had been discarded at a restart before it was resolved)
 constexpr int KSQ_ROUNDS = 44;  // cap on the squarings of one Schur vector (2^44 steps of the projected map)
 constexpr double KMARGIN = 100.0;
-
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 cmulc(double2 a, double2 b) { return make_double2(a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x); }   // conj(a) b
-__device__ __forceinline__ void cfma(double2 a, double2 b, double2& c) {   // c += a b
-  c.x = dfma(a.x, b.x, c.x);
-  c.x = dfma(-a.y, b.y, c.x);
-  c.y = dfma(a.x, b.y, c.y);
-  c.y = dfma(a.y, b.x, c.y);
-}
-__device__ __forceinline__ void cfms(double2 a, double2 b, double2& c) {   // c -= a b
-  c.x = dfma(-a.x, b.x, c.x);
-  c.x = dfma(a.y, b.y, c.x);
-  c.y = dfma(-a.x, b.y, c.y);
-  c.y = dfma(-a.y, b.x, c.y);
-}
-__device__ __forceinline__ void cfma_conj(double2 a, double2 b, double2& c) {   // c += a conj(b)
-  c.x = dfma(a.x, b.x, c.x);
-  c.x = dfma(a.y, b.y, c.x);
-  c.y = dfma(a.y, b.x, c.y);
-  c.y = dfma(-a.x, b.y, c.y);
-}
-__device__ __forceinline__ void cfma_cj(double2 a, double2 b, double2& c) {   // c += conj(a) b
-  c.x = dfma(a.x, b.x, c.x);
-  c.x = dfma(a.y, b.y, c.x);
-  c.y = dfma(a.x, b.y, c.y);
-  c.y = dfma(-a.y, b.x, c.y);
-}
-
-// complex 16 x 16 x 16 products on v_mfma_f64_16x16x4 (as in qmps_overlap.hip): P in A-layout, Q in B-layout, C-layout result
-__device__ __forceinline__ void cmma16(const double (&pre)[4], const double (&pim)[4], const v4f64& qre, const v4f64& qim, v4f64& cre, v4f64& cim) {
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    cre = __builtin_amdgcn_mfma_f64_16x16x4f64(pre[kk], qre[kk], cre, 0, 0, 0);
-    cim = __builtin_amdgcn_mfma_f64_16x16x4f64(pre[kk], qim[kk], cim, 0, 0, 0);
-    cre = __builtin_amdgcn_mfma_f64_16x16x4f64(-pim[kk], qim[kk], cre, 0, 0, 0);
-    cim = __builtin_amdgcn_mfma_f64_16x16x4f64(pim[kk], qre[kk], cim, 0, 0, 0);
-  }
-}
-__device__ __forceinline__ void cmma16_3m(const double (&pre)[4], const double (&pim)[4], const v4f64& qre, const v4f64& qim, v4f64& cre, v4f64& cim) {
-  v4f64 k1 = {0, 0, 0, 0}, k2 = {0, 0, 0, 0}, k3 = {0, 0, 0, 0};
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const double ps = pre[kk] + pim[kk], qd = qim[kk] - qre[kk], qs = qre[kk] + qim[kk];
-    k1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ps, qre[kk], k1, 0, 0, 0);
-    k2 = __builtin_amdgcn_mfma_f64_16x16x4f64(pre[kk], qd, k2, 0, 0, 0);
-    k3 = __builtin_amdgcn_mfma_f64_16x16x4f64(pim[kk], qs, k3, 0, 0, 0);
-  }
-  cre += k1 - k3;
-  cim += k1 + k2;
-}
 
 // ---- LDS map (bytes), one candidate per workgroup ------------------------------------------------------------------------
 template <int D>

@@ -40,28 +40,9 @@ struct D8Work {
 
 __device__ __forceinline__ void wsync() { __builtin_amdgcn_wave_barrier(); }
 
-template <int PATTERN>
-__device__ __forceinline__ double swz(double v) {      // value of the lane (own index xor mask), within groups of 32 lanes
-  const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), PATTERN);
-  const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), PATTERN);
-  return __hiloint2double(hi, lo);
-}
-
 struct Amp {
   double re[2], im[2];
 };
-
-// rx on the qubit whose bit is the lane-index bit selected by PATTERN: a' = c a - i s (partner's a), both local amplitudes
-template <int PATTERN>
-__device__ __forceinline__ void rx_cross(Amp& v, double c, double s) {
-#pragma unroll
-  for (int l = 0; l < 2; ++l) {
-    const double pr = swz<PATTERN>(v.re[l]), pi = swz<PATTERN>(v.im[l]);
-    const double nr = dfma(c, v.re[l], s * pi), ni = dfma(c, v.im[l], -s * pr);
-    v.re[l] = nr;
-    v.im[l] = ni;
-  }
-}
 
 // ShallowCNOTStateTensor (KIND 0) / ShallowCNOTStateTensor3 (KIND 3) at D = 8 (qmps/represent.py:288-310, 334-354): column j of the
 // 4-qubit circuit on |0>|j>, distributed over the lanes 8 j + a; writes A[s][i][j] = amplitude[2 i + s] into w.sA.
@@ -110,9 +91,12 @@ __device__ __forceinline__ void build_tensor_d8(D8Work& w, Par par, int n_params
       const double r0 = dfma(c, v.re[0], s * v.im[1]), i0 = dfma(c, v.im[0], -s * v.re[1]);
       const double r1 = dfma(c, v.re[1], s * v.im[0]), i1 = dfma(c, v.im[1], -s * v.re[0]);
       v.re[0] = r0; v.im[0] = i0; v.re[1] = r1; v.im[1] = i1;
-      rx_cross<0x041F>(v, c, s);     // q2 <-> a bit 0
-      rx_cross<0x081F>(v, c, s);     // q1 <-> a bit 1
-      rx_cross<0x101F>(v, c, s);     // q0 <-> a bit 2
+      rx_lanes<0x041F>(v.re[0], v.im[0], c, s);     // q2 <-> a bit 0, both local amplitudes
+      rx_lanes<0x041F>(v.re[1], v.im[1], c, s);
+      rx_lanes<0x081F>(v.re[0], v.im[0], c, s);     // q1 <-> a bit 1, both local amplitudes
+      rx_lanes<0x081F>(v.re[1], v.im[1], c, s);
+      rx_lanes<0x101F>(v.re[0], v.im[0], c, s);     // q0 <-> a bit 2, both local amplitudes
+      rx_lanes<0x101F>(v.re[1], v.im[1], c, s);
     }
     if (KIND == 3) rz_all(w.cs[l0 + 2][0], w.cs[l0 + 2][1]);
     {
@@ -120,7 +104,7 @@ __device__ __forceinline__ void build_tensor_d8(D8Work& w, Par par, int n_params
       const double h = 0.70710678118654752, sg = (a & 4) ? -h : h;
 #pragma unroll
       for (int l = 0; l < 2; ++l) {
-        const double pr = swz<0x101F>(v.re[l]), pi = swz<0x101F>(v.im[l]);
+        const double pr = swz32<0x101F>(v.re[l]), pi = swz32<0x101F>(v.im[l]);
         v.re[l] = dfma(sg, v.re[l], h * pr);
         v.im[l] = dfma(sg, v.im[l], h * pi);
       }
@@ -145,7 +129,7 @@ __device__ __forceinline__ void build_tensor_d8(D8Work& w, Par par, int n_params
 // ||r' - r||_F < tol, LDL^H pivots > 0, E = sum over the Hamiltonian terms (the reference's M(x) = np.sum(eps), qmps/tools.py:432-433):
 // hsum is the SUM of the terms' 4 x 4 matrices, staged in LDS once per run (E is linear in h; fetching the terms from HBM
 // inside every evaluation cost ~1 us of latency).
-// The arithmetic of energy_block_kernel<8, true, FUSED> (qmps_kernels.hip) with wave-local synchronisation.
+// The arithmetic of energy_block_kernel<8, true, FUSED> (qmps_energy_block.hip) with wave-local synchronisation.
 __device__ __forceinline__ double eval_d8(D8Work& w, const double2* hsum, int max_iter, double tol, int lane,
                                           int& status_out, long long* prof = nullptr, int* iters_out = nullptr) {
   constexpr int D = 8;

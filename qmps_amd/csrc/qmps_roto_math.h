@@ -1,5 +1,5 @@
 // qmps_roto_math.h - the update rules of the rotosolve drivers (gfx950 only), shared by roto_update_kernel, the whole-run
-// D = 2 kernel (qmps_kernels.hip) and the whole-run D = 8 kernel (qmps_roto_d8.hip).
+// D = 2 kernel (qmps_energy_lane.hip) and the whole-run D = 8 kernel (qmps_roto_d8.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -17,19 +17,9 @@
 
 #include "qmps_kernels.h"
 #include "qmps_device.h"
+#include "qmps_complex.h"
 
 namespace qmps {
-
-namespace {
-
-__device__ __forceinline__ void cfma(double2 a, double2 b, double2& c) {   // c += a b
-  c.x = dfma(a.x, b.x, c.x);
-  c.x = dfma(-a.y, b.y, c.x);
-  c.y = dfma(a.x, b.y, c.y);
-  c.y = dfma(a.y, b.x, c.y);
-}
-
-}  // namespace
 
 // out_tensor != 0: A[b][2][N/2][N/2] (the first N/2 columns of U, rows split as 2 i + s);  else U[b][N][N]
 template <int N>

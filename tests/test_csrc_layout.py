@@ -1,0 +1,43 @@
+"""CPU: source checks of qmps_amd/csrc - the library is built from exactly the translation units that are there, and every small
+device helper has one definition."""
+import glob
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, 'qmps_amd', 'csrc')
+
+SHARED_HELPERS = ('cmul', 'cmulc', 'cfma', 'cfms', 'cfma_conj', 'cfma_cj', 'cmma16', 'cmma16_3m', 'swz32', 'rx_lanes')
+
+
+def sources():
+    files = sorted(glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(CSRC, '*.hip')))
+    assert len(files) > 30
+    return {os.path.basename(f): open(f).read() for f in files}
+
+
+def test_makefile_builds_exactly_the_translation_units_present():
+    """SRCS is an explicit list (a stray scratch file never enters the library) and it names every *.hip file, once."""
+    make = open(os.path.join(CSRC, 'Makefile')).read().replace('\\\n', ' ')
+    srcs = re.search(r'^SRCS\s*:=\s*(.*)$', make, flags=re.M).group(1).split()
+    assert len(srcs) == len(set(srcs))
+    assert sorted(srcs) == sorted(os.path.basename(f) for f in glob.glob(os.path.join(CSRC, '*.hip')))
+    assert 'wildcard' not in ' '.join(srcs)
+    # every header is a dependency of every object: a new header cannot be a silently missing one
+    rule = re.search(r'^build/%\.o:\s*(.*)$', make, flags=re.M).group(1)
+    assert '$(wildcard *.h)' in rule and '../../include/qmps_hip.h' in rule
+    assert not os.path.exists(os.path.join(CSRC, 'qmps_kernels.hip'))
+
+
+def test_each_shared_device_helper_is_defined_once():
+    src = sources()
+    for name in SHARED_HELPERS:
+        where = [f for f, text in src.items()
+                 for _ in re.findall(r'__device__ __forceinline__ [\w:]+ %s\(' % re.escape(name), text)]
+        assert len(where) == 1, f'{name}: defined in {where}'
+    for f, text in src.items():
+        # the names the copies used to hide behind
+        assert 'cfma_conj1' not in text, f
+        assert not re.search(r'\bcmma\(', text), f
+        assert not re.search(r'\bswz<', text), f
+        assert not re.search(r'\brx_cross\b', text), f
