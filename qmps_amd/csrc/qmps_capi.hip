@@ -5,6 +5,7 @@
 // qmps_capi_brickwall.hip; the peak probes: qmps_capi_probe.hip; the time-evolution overlap objective: qmps_capi_overlap.hip; the
 // evolve drivers: qmps_capi_evolve.hip; the rotosolve drivers: qmps_capi_roto.hip.
 #include "qmps_ctx.h"
+#include "qmps_direct_core.h"
 
 using namespace qmps_host;
 
@@ -447,6 +448,7 @@ int qmps_set_hamiltonian(qmps_ctx* c, int n_terms, const double* h) try {
     f = sqrt(f);
     if (f > c->h_fro) c->h_fro = f;
   }
+  c->rho_need = qmps::rho_need_mask(h, n_terms);
   if (n_terms != c->n_terms) {
     // The in-kernel clear of a cost accumulator covers the CURRENT number of terms only: after a change of that number a slot that counts as clean
     // may still hold the arrivals of a term it was last used with ("cost accumulator: 46 of 23 waves arrived" on the first accumulating launch after

@@ -4,6 +4,7 @@
 // qmps_capi.hip, qmps_ctx.h.  Where an accumulated cost goes (setup_accumulator, qmps_cost_launch): qmps_capi_cost.hip.  The
 // rotosolve drivers built on these launches: qmps_capi_roto.hip.
 #include "qmps_ctx.h"
+#include "qmps_direct_core.h"
 
 using namespace qmps_host;
 
@@ -20,6 +21,7 @@ qmps::LaneArgs make_args(qmps_ctx* c, int64_t B, int max_iter, double tol, bool 
   a.r_in = solve ? (c->have_guess ? win_r(c) : nullptr) : win_r(c);
   a.r_out = solve ? win_r(c) : nullptr;
   a.rho_out = c->want_rho ? (char*)c->d_rho + (size_t)c->window * 256 : nullptr;
+  a.rho_need = a.rho_out != nullptr ? qmps::kRhoNeedAll : c->rho_need;   // rho itself: every entry; otherwise what h reads
   a.E = win_E(c);
   a.iters = win_iters(c);
   a.status = win_status(c);

@@ -132,7 +132,7 @@ int step_by_step(qmps_ctx* c, const RotoRun& r) {
   const bool use_graph = use_sweep_graph(r.P);
   if (use_graph) {
     qmps_ctx::RotoKey key;
-    key.R = r.R; key.kind = r.kind; key.P = r.P; key.nsh = r.nsh; key.max_iter = r.max_iter; key.n_terms = c->n_terms;
+    key.R = r.R; key.kind = r.kind; key.P = r.P; key.nsh = r.nsh; key.max_iter = r.max_iter; key.n_terms = c->n_terms; key.rho_need = c->rho_need;
     key.solver = c->default_solver; key.handoff = c->handoff; key.rule = c->roto_rule; key.tol = r.tol; key.fused = fused;
     key.base = r.base; key.hist = r.hist; key.params = c->d_params; key.E = c->d_E;
     if (!(c->roto_exec && key == c->roto_key)) {

@@ -185,11 +185,12 @@ struct qmps_ctx {
   struct RotoKey {
     int64_t R = -1;
     int kind = 0, P = 0, nsh = 0, max_iter = 0, n_terms = 0, solver = 0, handoff = 0, rule = 0;
+    uint32_t rho_need = 0;      // the captured energy launches carry it in their arguments (h itself is read from d_h when they run)
     double tol = 0.0;
     bool fused = false;
     const void *base = nullptr, *hist = nullptr, *params = nullptr, *E = nullptr;
     bool operator==(const RotoKey& o) const {
-      return R == o.R && kind == o.kind && P == o.P && nsh == o.nsh && max_iter == o.max_iter && n_terms == o.n_terms && solver == o.solver &&
+      return R == o.R && kind == o.kind && P == o.P && nsh == o.nsh && max_iter == o.max_iter && n_terms == o.n_terms && rho_need == o.rho_need && solver == o.solver &&
              handoff == o.handoff && rule == o.rule && tol == o.tol && fused == o.fused && base == o.base && hist == o.hist && params == o.params && E == o.E;
     }
   } roto_key;
@@ -235,6 +236,7 @@ struct qmps_ctx {
   int64_t acc_B = 0, acc_window = 0;
   int acc_slot = 0, acc_pos = 0;
   double h_fro = 0.0;                        // max_t ||h_t||_F (qmps_set_hamiltonian)
+  uint32_t rho_need = 0xFFFFFFFFu;           // qmps::rho_need_mask of the resident Hamiltonian (qmps_set_hamiltonian)
   long long* acc_at(int slot, int pos) const { return d_acc + ((size_t)slot * kMaxGroup + pos) * qmps::kAccWords; }
 };
 

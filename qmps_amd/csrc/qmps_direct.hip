@@ -6,7 +6,8 @@
 //   -> (R - 1 + e_15 t^T) u = e_15 by Gauss-Jordan elimination in registers, pivot rows handed round the quad by
 //      v_mov_b32_dpp quad_perm (VALU only; no LDS, no cross-quad traffic)
 //   -> one power step as acceptance test (||T(r) - r||_F < tol; else the power method 2^m steps at a time)
-//   -> LDL^H positive-definiteness test, two-site density matrix, energies of all Hamiltonian terms
+//   -> LDL^H positive-definiteness test, two-site density matrix - of its upper triangle the real and imaginary parts that some
+//      term of h reads (LaneArgs::rho_need; all of it when rho is returned) - energies of all Hamiltonian terms, h from scalar loads
 //   -> E (8 B per term), iterations + status (8 B), optionally r (256 B); per-wave partial sums of E.
 // One read of A and one store of E per evaluation: the environment never travels through HBM.
 // The mathematics lives in qmps_direct_core.h (shared with the CPU lock-step emulation the test-suite uses).
@@ -86,6 +87,12 @@ struct QuadOps {
     im = v.y;
   }
 };
+
+// The Hamiltonian as the energy sums read it: wave-uniform and constant for the launch - it is written only by qmps_set_hamiltonian, through
+// a copy ordered on the context stream before every launch that reads it - so the loads may go through the constant address space: scalar
+// loads into scalar registers (s_load_dwordx2 .. x16), where a generic pointer costs every lane a vector load of the same address per entry.
+typedef const __attribute__((address_space(4))) double* const_f64_ptr;
+__device__ __forceinline__ const_f64_ptr h_term(const void* h, int t) { return (const_f64_ptr)(uintptr_t)h + 32 * t; }
 
 // The rare path (tensors that are not isometries, degenerate transfer spectra): the power method 2^m steps at a time,
 // ONE EVALUATION AT A TIME WITH THE WHOLE WAVE ON THE MATRIX CORES.  In orthonormal Hermitian coordinates
@@ -364,11 +371,12 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
 
   // ---- positive definiteness, two-site density matrix, energies ----
   double pre[4][4], pim[4][4];
-  const bool pd = Core::density(o, us, pre, pim);
+  // (p.rho_need: the parts of rho some term of h reads; everything when rho itself is asked for)
+  const bool pd = Core::density(o, us, p.rho_need, pre, pim);
   if (status == QMPS_ST_OK && !pd) status = QMPS_ST_NOT_PD;
   if (p.acc_zero != nullptr && blockIdx.x == 0) acc_clear(p.acc_zero, p.n_terms, lane, 64);   // accumulator of a later step
   for (int t = 0; t < p.n_terms; ++t) {
-    const double en = quad_sum(Core::energy((const double*)p.h + 32 * t, pre, pim));
+    const double en = quad_sum(Core::energy(h_term(p.h, t), p.rho_need, pre, pim));
     if (valid && q == 0) p.E[b * p.n_terms + t] = en;
     if (p.partial != nullptr || p.acc != nullptr) {
       const double s = wave_sum((valid && q == 0) ? en : 0.0);
@@ -478,7 +486,7 @@ __global__ __launch_bounds__(64, LEAN ? QMPS_ENERGY_ONLY_LEAN_WAVES : 2) void en
       Core::gather(x, us);
     } else {
       Core::gather(x, us);
-      pd = Core::density(o, us, pre, pim);
+      pd = Core::density(o, us, p.rho_need, pre, pim);
     }
     int status = QMPS_ST_OK;
     if (p.check_pd) {
@@ -488,7 +496,7 @@ __global__ __launch_bounds__(64, LEAN ? QMPS_ENERGY_ONLY_LEAN_WAVES : 2) void en
     for (int t = 0; t < p.n_terms; ++t) {
       double en;
       if constexpr (LEAN) en = quad_sum(Core::energy_lean(bre, bim, us, (const double*)p.h + 32 * t));
-      else en = quad_sum(Core::energy((const double*)p.h + 32 * t, pre, pim));
+      else en = quad_sum(Core::energy(h_term(p.h, t), p.rho_need, pre, pim));
       if (valid && q == 0) p.E[b * p.n_terms + t] = en;
       if (p.partial != nullptr || p.acc != nullptr) {
         const double s = wave_sum((valid && q == 0) ? en : 0.0);

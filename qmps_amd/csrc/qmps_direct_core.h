@@ -30,9 +30,29 @@
 //           o.uni(s, i, j, re, im) A_s[i][j]  (the same value in every lane of the quad)
 #pragma once
 
+#include <stdint.h>
+
 #include <utility>
 
 namespace qmps {
+
+// Which entries of the upper triangle of rho the Hamiltonian reads (E = Re sum h[s][t] rho[t][s]): bit 4 t + s (t <= s) - the real part of
+// rho[t][s] - is set iff some term has Re h[s][t] != 0 or Re h[t][s] != 0, bit 16 + 4 t + s (t < s) - the imaginary part - iff some term has
+// Im h[s][t] != 0 or Im h[t][s] != 0.  Exact comparisons: -0.0 is zero, NaN is needed.  h: n_terms x 16 complex numbers (re, im interleaved),
+// Hermitian or not.  Plain C++: the host computes it once per Hamiltonian (qmps_set_hamiltonian).
+constexpr uint32_t kRhoNeedAll = 0xFFFFFFFFu;
+inline uint32_t rho_need_mask(const double* h, int n_terms) {
+  uint32_t need = 0;
+  for (int n = 0; n < n_terms; ++n)
+    for (int s = 0; s < 4; ++s)
+      for (int t = 0; t < 4; ++t) {
+        const int lo = t < s ? t : s, hi = t < s ? s : t;
+        const double re = h[32 * n + 2 * (4 * s + t)], im = h[32 * n + 2 * (4 * s + t) + 1];
+        if (!(re == 0.0)) need |= 1u << (4 * lo + hi);
+        if (lo != hi && !(im == 0.0)) need |= 1u << (16 + 4 * lo + hi);
+      }
+  return need;
+}
 
 #if defined(__HIPCC__)
 #define QMPS_CORE_FN __device__ inline __attribute__((always_inline))
@@ -43,6 +63,13 @@ namespace qmps {
 #else
 #define QMPS_CORE_FN inline __attribute__((always_inline))
 #define QMPS_SCHED_FENCE() ((void)0)
+#endif
+// "this value exists here": in front of code that branches, the compiler otherwise sinks the arithmetic that produces a value into the
+// branch that first reads it and leaves the LDS reads behind it in flight - their data then fills the register file across the branches
+#if defined(__HIP_DEVICE_COMPILE__)
+#define QMPS_COMPUTED_HERE(v) asm volatile("" : "+v"(v))
+#else
+#define QMPS_COMPUTED_HERE(v) ((void)0)
 #endif
 
 template <int... I, class F>
@@ -389,6 +416,11 @@ struct DirectD4 {
   //         lane's share of the two-site density matrix rho[tau][sigma] = tr(B_tau r B_sigma^+), tau <= sigma ----
   // us: all sixteen coordinates of r (trace 1).  Lane q contributes row q of B_tau = A_t1 A_t2 (tau = 2 t1 + t2).
   static QMPS_CORE_FN P density(const O& o, const V (&us)[16], V (&pre)[4][4], V (&pim)[4][4]) {
+    return density(o, us, kRhoNeedAll, pre, pim);
+  }
+  // need (rho_need_mask; the same for every lane of the wave): an entry whose bit is clear is not computed and left exactly 0.0 - in both
+  // routes; the entries that are computed see the same operations in the same order whatever the mask
+  static QMPS_CORE_FN P density(const O& o, const V (&us)[16], uint32_t need, V (&pre)[4][4], V (&pim)[4][4]) {
     // r[k][l], k <= l
     V rre[4][4], rim[4][4];
 #pragma unroll
@@ -445,6 +477,7 @@ struct DirectD4 {
         bre[tau][k] = cr;      // (column k reads B[i], i > k: not overwritten yet)
         bim[tau][k] = ci;
       }
+    computed_here(bre, bim);       // (the tests of rho_row follow)
 #pragma unroll
     for (int tau = 0; tau < 4; ++tau) {
       V gre[4], gim[4];
@@ -453,7 +486,7 @@ struct DirectD4 {
         gre[k] = bre[tau][k] * d[k];
         gim[k] = bim[tau][k] * d[k];
       }
-      rho_row(tau, gre, gim, bre, bim, pre, pim);
+      rho_row(tau, need, gre, gim, bre, bim, pre, pim);
     }
     // An r that fails the test is not what its factors give back (a pivot <= 0 was replaced by 1 above).  Those evaluations
     // take rho from Y_tau = (row q of B_tau) r instead: a rare branch, uniform over the wave on the device, in which every
@@ -461,6 +494,7 @@ struct DirectD4 {
     QMPS_SCHED_FENCE();
     if (O::any(O::p_not(pd))) {
       b_rows(o, bre, bim);
+      computed_here(bre, bim);
 #pragma unroll
       for (int tau = 0; tau < 4; ++tau) {
         V yre[4], yim[4];
@@ -481,9 +515,11 @@ struct DirectD4 {
           }
           yre[l] = cr;
           yim[l] = ci;
+          QMPS_COMPUTED_HERE(yre[l]);
+          QMPS_COMPUTED_HERE(yim[l]);
         }
         V qre[4][4], qim[4][4];
-        rho_row(tau, yre, yim, bre, bim, qre, qim);
+        rho_row(tau, need, yre, yim, bre, bim, qre, qim);
 #pragma unroll
         for (int sg = tau; sg < 4; ++sg) {
           pre[tau][sg] = O::sel(pd, pre[tau][sg], qre[tau][sg]);
@@ -495,45 +531,90 @@ struct DirectD4 {
     return pd;
   }
 
+  static QMPS_CORE_FN void computed_here(V (&bre)[4][4], V (&bim)[4][4]) {
+#pragma unroll
+    for (int tau = 0; tau < 4; ++tau)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        QMPS_COMPUTED_HERE(bre[tau][k]);
+        QMPS_COMPUTED_HERE(bim[tau][k]);
+      }
+  }
+
   // rho[tau][sigma] += sum_l Y[l] conj(B_sigma[l]), sigma >= tau: the lane's share of row tau of rho
   static QMPS_CORE_FN void rho_row(int tau, const V (&yre)[4], const V (&yim)[4], const V (&bre)[4][4], const V (&bim)[4][4],
                                    V (&pre)[4][4], V (&pim)[4][4]) {
+    rho_row(tau, kRhoNeedAll, yre, yim, bre, bim, pre, pim);
+  }
+  // ... of which only the parts `need` (rho_need_mask) asks for: a whole real or imaginary part (eight multiply-adds) per test
+  static QMPS_CORE_FN void rho_row(int tau, uint32_t need, const V (&yre)[4], const V (&yim)[4], const V (&bre)[4][4],
+                                   const V (&bim)[4][4], V (&pre)[4][4], V (&pim)[4][4]) {
 #pragma unroll
     for (int sg = tau; sg < 4; ++sg) {
-      V cr = yre[0] * bre[sg][0], ci = O::splat(0.0);
-      cr = O::fma(yim[0], bim[sg][0], cr);
+      V cr = O::splat(0.0);
+      if ((need >> (4 * tau + sg)) & 1u) {
+        cr = yre[0] * bre[sg][0];
+        cr = O::fma(yim[0], bim[sg][0], cr);
 #pragma unroll
-      for (int l = 0; l < 4; ++l) {
-        if (l > 0) {
+        for (int l = 1; l < 4; ++l) {
           cr = O::fma(yre[l], bre[sg][l], cr);
           cr = O::fma(yim[l], bim[sg][l], cr);
         }
-        if (sg != tau) {
-          ci = O::fma(yim[l], bre[sg][l], ci);
-          ci = O::fma(-yre[l], bim[sg][l], ci);
-        }
       }
       pre[tau][sg] = cr;
-      pim[tau][sg] = ci;
+      pim[tau][sg] = O::splat(0.0);
+    }
+    // (the imaginary parts of the row behind one test of their own: a real Hamiltonian passes three tests, not six, and what the parts
+    // share - the negated Y - stays inside)
+    if ((need >> (16 + 4 * tau)) & 0xFu) {
+#pragma unroll
+      for (int sg = tau + 1; sg < 4; ++sg)
+        if ((need >> (16 + 4 * tau + sg)) & 1u) {
+          V ci = O::splat(0.0);
+#pragma unroll
+          for (int l = 0; l < 4; ++l) {
+            ci = O::fma(yim[l], bre[sg][l], ci);
+            ci = O::fma(-yre[l], bim[sg][l], ci);
+          }
+          pim[tau][sg] = ci;
+        }
     }
   }
 
   // E = Re sum_{s,t} h[s][t] rho[t][s] from the upper triangle of rho; h: 16 complex numbers (re, im interleaved),
   // the same for every lane
   static QMPS_CORE_FN V energy(const double* h, const V (&pre)[4][4], const V (&pim)[4][4]) {
+    return energy(h, kRhoNeedAll, pre, pim);
+  }
+  // ... for a rho that density(need) left: without the multiply-adds of the imaginary parts when `need` holds none of them (every real
+  // Hamiltonian) - one test for all twelve, two straight-line sums.  A part that `need` leaves out is exactly 0.0 and so is its h in every
+  // term: whether it is multiplied or not, it adds +-0.0, which changes no bit of the sum - E is the full contraction's bit for bit.  (A test
+  // per multiply-add, which the single real parts would need, costs the device more than the multiply-add: it is compiled to a select.)
+  // H: const double*, or what reads like one (the device reads h through the constant address space: scalar loads)
+  template <class H>
+  static QMPS_CORE_FN V energy(H h, uint32_t need, const V (&pre)[4][4], const V (&pim)[4][4]) {
     V e = O::splat(0.0);
+    if ((need >> 16) != 0u) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
+      for (int s = 0; s < 4; ++s) {
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const double hr = h[2 * (4 * s + t)], hi = h[2 * (4 * s + t) + 1];
-        const V rr = t <= s ? pre[t][s] : pre[s][t];
-        e = O::fma(O::splat(hr), rr, e);
-        if (t != s) {
-          const V ri = t < s ? pim[t][s] : -pim[s][t];
-          e = O::fma(O::splat(-hi), ri, e);
+        for (int t = 0; t < 4; ++t) {
+          const double hr = h[2 * (4 * s + t)], hi = h[2 * (4 * s + t) + 1];
+          const V rr = t <= s ? pre[t][s] : pre[s][t];
+          e = O::fma(O::splat(hr), rr, e);
+          if (t != s) {
+            const V ri = t < s ? pim[t][s] : -pim[s][t];
+            e = O::fma(O::splat(-hi), ri, e);
+          }
         }
+        QMPS_COMPUTED_HERE(e);     // (a row of h at a time: all of it would not fit the device's scalar registers beside the rest)
       }
+    } else {
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) e = O::fma(O::splat(h[2 * (4 * s + t)]), t <= s ? pre[t][s] : pre[s][t], e);
+    }
     return e;
   }
 };

@@ -31,6 +31,9 @@ struct LaneArgs {
   int n_terms;
   int max_iter;
   double tol;
+  // D = 4 quad kernels (energy_direct_d4_kernel, energy_only_d4_kernel): the parts of the upper triangle of rho that some term of h reads
+  // (qmps::rho_need_mask, qmps_direct_core.h); the others are neither computed nor multiplied.  All ones whenever rho_out is set.
+  uint32_t rho_need;
   // hybrid solve: `handoff` plain power steps, then the repeated-squaring tail (0 = plain only)
   int handoff;
   int hybrid;                 // 1: squaring tail enabled (handoff may be 0 = squaring from the start)
