@@ -193,7 +193,8 @@ int qmps_abi_version(void);
  *      status that is not usable beats QMPS_STATUS_TIED (a max let TIED hide NOT_CONVERGED).  qmps_evolve_bfgs at D = 4 eigen-solves the 2 n_params
  *      neighbours of its tied iterates one by one, as qmps_evolve_bfgs_device does.
  * 6.7: qmps_ansatz_probe (the tensors of the device ansatz builders: plain, rotosolve-shifted and central-difference batches; test hook).
- *      Added later without a bump (detect it by the symbol's presence): qmps_correlators, the two-point functions of the resident states. */
+ *      Added later without a bump (detect them by the symbol's presence): qmps_correlators, the two-point functions of the resident states;
+ *      qmps_entanglement, their Schmidt spectra and entanglement entropies. */
 int qmps_abi_minor(void);
 const char* qmps_last_error(void);
 /* Test hook for the contract above ("nothing throws across the ABI"): raises a C++ exception inside the library - kind 1
@@ -360,6 +361,28 @@ int qmps_get_rdm(qmps_ctx* ctx, int64_t B, double* rho);
 int qmps_correlators(qmps_ctx* ctx, int64_t B, int n_ops, const double* ops /* [n_ops][2][2] complex128 */, int n_max,
                      double* C_out   /* [B][n_ops][n_ops][n_max] complex128 */,
                      double* one_out /* nullable, [B][n_ops] complex128 */);
+/* Entanglement (Schmidt) spectrum of the resident states [window, window + B) from their resident environments (nothing is solved):
+ *   p_out[b][k]    = k-th largest eigenvalue of herm(r_b) / tr r_b, k = 0 .. D-1 (descending; signed: an environment that is
+ *                    not positive definite shows its negative eigenvalues),  herm(r) = (r + r^+) / 2
+ *   S_out[b]       = - sum_(p > 0) p ln p   (von Neumann entropy in nats; eigenvalues <= 0 contribute nothing)
+ *   V_out[b][i][k] = component i of the unit eigenvector belonging to p_out[b][k]  (herm(r) V = tr(r) V diag(p), V^+ V = 1; with
+ *                    A_s -> V^+ A_s V the environment becomes diagonal; the columns of tied eigenvalues are any orthonormal basis)
+ * For the left isometries this library builds (sum_s A_s^+ A_s = 1) the p are the squared Schmidt coefficients of the half-chain
+ * cut.  The left environment is taken to be the identity, as in qmps_get_rdm and qmps_correlators: for tensors that are not left
+ * isometries p is still the spectrum of r / tr r.  r of any non-zero finite trace is normalised; the status of the solve that
+ * produced r is not consulted (qmps_get_status).  An evaluation whose tr r is zero or not finite, or which holds a non-finite
+ * element, yields NaN in all of its outputs and leaves its neighbours alone.
+ * Method: cyclic complex-Hermitian Jacobi (round-robin order) on the device, to off(A)^2 <= 2^-104 sum a_ii^2.  A pivot with
+ * |a_pq|^2 < 2^-960 or |a_pq|^2 <= 2^-102 |a_pp a_qq| (rounding noise between tied eigenvalues) is set to zero without a rotation.
+ * At most 1 / 10 / 24 / 30 sweeps at D = 2 / 4 / 8 / 16, NaN for an evaluation that is not done by then: D = 2 is one rotation,
+ * exact; a float64 port needed at most 4 / 12 / 14 sweeps on well- and ill-conditioned spectra and on clusters of 2 .. D tied
+ * eigenvalues, so the caps hold a margin of two.  Eigenvalues within a few D 2^-52 (absolute, of a unit-trace matrix).
+ * QMPS_ERR_STATE when no environment is resident (also after a launch with QMPS_FLAG_NO_ENV_OUT) or the window runs past the resident
+ * states; B = 0 writes nothing.  One kernel launch (the variant without eigenvectors when V_out is NULL); synchronous, with one
+ * synchronisation at the read-back.  Resident states, parameters, environments, energies, iteration counts and statuses stay exactly
+ * as they are. */
+int qmps_entanglement(qmps_ctx* ctx, int64_t B, double* p_out /* [B][D] */, double* S_out /* nullable, [B] */,
+                      double* V_out /* nullable, [B][D][D] complex128 */);
 
 /* ---- one-shot host-buffer convenience (SURVEY 8(b) energy_batch / env_batch) ------------ */
 int qmps_energy_batch(qmps_ctx* ctx, int64_t B, const double* states, int kind, const double* h, int n_terms,

@@ -443,5 +443,14 @@ struct CorrelatorArgs {
   int n_ops, n_max;    // 1 <= n_ops <= 4, n_max >= 1
 };
 hipError_t launch_correlators(int D, const CorrelatorArgs& a, hipStream_t st);
+// Schmidt spectra of the resident states (qmps_entanglement.hip): batched complex-Hermitian Jacobi, one launch
+struct EntanglementArgs {
+  const void* r;       // [B][D][D] complex right environments (herm(r) / tr r is diagonalised)
+  double* p;           // [B][D] eigenvalues, descending
+  double* S;           // [B] - sum_(p > 0) p ln p
+  void* V;             // nullable [B][D][D] complex: V[i][k] = component i of the eigenvector of p[k] (null: the variant without them)
+  int64_t B;
+};
+hipError_t launch_entanglement(int D, const EntanglementArgs& a, hipStream_t st);
 
 }  // namespace qmps

@@ -275,6 +275,21 @@ class EnergyEngine:
                                            None if one is None else _f64(one.view(np.float64))))
         return (C, one) if want_one_site else C
 
+    def entanglement(self, B=None, want_vectors=False):
+        """Entanglement (Schmidt) spectra of the resident states from their resident environments (`launch` with the environments stored,
+        or `set_env_guess`; nothing is solved here): p[b, k] = k-th largest eigenvalue of herm(r_b) / tr r_b, shape (B, D), descending and
+        signed (an environment that is not positive definite shows its negative eigenvalues), and S[b] = - sum_(p > 0) p ln p in nats,
+        shape (B,).  want_vectors=True: returns (p, S, V) with V[b, :, k] the unit eigenvector of p[b, k], shape (B, D, D) complex128
+        (`A_s -> V^+ A_s V` makes r diagonal).  An r whose trace is zero or that is not finite gives NaN.  One kernel launch (a batched
+        Jacobi eigensolver; the variant without eigenvectors unless they are asked for), one synchronisation."""
+        B = self.B if B is None else int(B)
+        n = max(B, 0)
+        p = np.empty((n, self.D))
+        S = np.empty(n)
+        V = np.empty((n, self.D, self.D), dtype=np.complex128) if want_vectors else None
+        L.check(self._lib.qmps_entanglement(self._ctx, B, _f64(p), _f64(S), None if V is None else _f64(V.view(np.float64))))
+        return (p, S, V) if want_vectors else (p, S)
+
     def summed_cost(self, B=None):
         cost = np.empty(max(self.n_terms, 1))
         L.check(self._lib.qmps_sum_energies(self._ctx, self.B if B is None else B, _f64(cost)))

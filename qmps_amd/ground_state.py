@@ -437,3 +437,27 @@ def correlation_functions(params, ops, n_max, D=2, state_tensor=ShallowCNOTState
     if connected:
         C = C - (one[:, :, None] * one[:, None, :])[..., None]
     return C, one, status
+
+
+def entanglement_entropy(params, D=2, state_tensor=ShallowCNOTStateTensor):
+    """Half-chain entanglement of the states of K parameter rows - the companion of `ground_state_sweep` (params = out['params']) and
+    `correlation_functions`:
+      S (K,)        von Neumann entropy  - sum p ln p  of the cut, in nats (at most ln D)
+      p (K, D)      the Schmidt spectrum (squared Schmidt coefficients, descending): the eigenvalues of the right environment r / tr r
+      status (K,)   of the environment solve (STATUS_OK = 0; the spectrum of any other row is not to be trusted)
+    The tensors are built on the device for the ansatz classes libqmps_hip knows (`device_kind`), one environment solve runs with the
+    environments stored, and ONE launch of the Jacobi kernel diagonalises them where they are (`EnergyEngine.entanglement`).  Renyi
+    entropies are one line on p: ln(sum p^a) / (1 - a)."""
+    P = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float64)
+    K = P.shape[0]
+    kind = getattr(state_tensor, 'device_kind', None)
+    on_device = kind is not None and not (kind in (2, 6) and D != 2)
+    eng = _runtime.engine(D, K)
+    if on_device:
+        eng.set_ansatz_params(kind, P)
+    else:
+        eng.set_unitaries(np.stack([unitary(build_gate(state_tensor, D, p_)) for p_ in P]))
+    eng.set_hamiltonian(np.zeros((1, 4, 4), dtype=np.complex128))      # the launch wants a resident Hamiltonian: a single zero term
+    eng.launch(K, max_iter=_GpuEnergyMixin.max_iter, tol=_GpuEnergyMixin.env_tol, solver='direct', store_env=True, krylov_fallback=D >= 8)
+    p, S = eng.entanglement(B=K)
+    return S, p, eng.results_status(K)
