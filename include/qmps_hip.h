@@ -194,7 +194,8 @@ int qmps_abi_version(void);
  *      neighbours of its tied iterates one by one, as qmps_evolve_bfgs_device does.
  * 6.7: qmps_ansatz_probe (the tensors of the device ansatz builders: plain, rotosolve-shifted and central-difference batches; test hook).
  *      Added later without a bump (detect them by the symbol's presence): qmps_correlators, the two-point functions of the resident states;
- *      qmps_entanglement, their Schmidt spectra and entanglement entropies. */
+ *      qmps_entanglement, their Schmidt spectra and entanglement entropies; qmps_correlator_sums, the sums over all distances of their
+ *      connected two-point functions (structure factors). */
 int qmps_abi_minor(void);
 const char* qmps_last_error(void);
 /* Test hook for the contract above ("nothing throws across the ABI"): raises a C++ exception inside the library - kind 1
@@ -383,6 +384,33 @@ int qmps_correlators(qmps_ctx* ctx, int64_t B, int n_ops, const double* ops /* [
  * as they are. */
 int qmps_entanglement(qmps_ctx* ctx, int64_t B, double* p_out /* [B][D] */, double* S_out /* nullable, [B] */,
                       double* V_out /* nullable, [B][D][D] complex128 */);
+
+/* Correlator sums of the resident states [window, window + B) with their resident environments (nothing is solved) - the n >= 1 half
+ * of a structure factor, summed to infinity by one linear solve per (state, z) instead of a truncated chain of qmps_correlators.
+ * With E_O, T, O[t][s] as in qmps_correlators, tau = tr r and L_a = sum_(t,s) O_a[t][s] A_t^+ A_s:
+ *   one_out[b][a]     = tr(E_(O_a)(r)) / tau                                = <O_a>
+ *   site_out[b][a][c] = tr(E_(O_a O_c)(r)) / tau                            = <O_a O_c> on one site (the 2 x 2 matrix product)
+ *   b_c = E_(O_c)(r) - one[c] r,    Tt(x) = T(x) - r tr(x) / tau            (the transfer map with its fixed point projected out)
+ *   G_out[b][j][a][c] = z_j tr(L_a (1 - z_j Tt)^(-1)(b_c)) / tau
+ * which, for r the exact fixed point and |z| <= 1, is sum_(n >= 1) z_j^n (C[b][a][c][n-1] - one[b][a] one[b][c]) with C of
+ * qmps_correlators; the formula above is what is computed, also for an r that is a fixed point only to the solver's tolerance.  The
+ * static structure factor is composed by the caller:
+ *   S_ac(k) = site[a][c] - one[a] one[c] + G_ac(z = e^(-ik)) + G_ca(z = e^(+ik)).
+ * 1 <= n_ops <= 4, 1 <= n_z <= 1024, every |z_j|^2 <= 1 + 1e-12 (the slack is for e^(ik) as float64 rounds it), and G_out may not
+ * exceed 1 GiB: QMPS_ERR_ARG otherwise, with nothing written.  Null pointers, the window and a missing environment are treated as
+ * in qmps_correlators; B = 0 writes nothing.  Method: the matrix of 1 - z Tt, of order D^2, is built on the device and solved for the
+ * n_ops right-hand sides by Gauss-Jordan elimination with partial (row) pivoting, one (b, j) per lane (D = 2), per 16 lanes
+ * (D = 4) or per workgroup (D = 8 in LDS; D = 16 in a device workspace of at most 252 matrices of 1040 KiB, over which a fixed grid of
+ * workgroups strides).  The error is a few 2^-52 ||(1 - z Tt)^(-1)||, independent of how slowly the correlations decay.
+ * An evaluation whose tr r is zero or not finite yields NaN in all its outputs.  A (b, j) whose elimination meets a pivot that is
+ * zero or not finite - the singular resolvent of a degenerate fixed point at |z| = 1 - yields NaN in G_out[b][j] alone.
+ * One kernel launch; synchronous, with one synchronisation at the read-back.  Resident states, parameters, environments, energies,
+ * iteration counts and statuses stay exactly as they are. */
+int qmps_correlator_sums(qmps_ctx* ctx, int64_t B, int n_ops, const double* ops /* [n_ops][2][2] complex128 */,
+                         int n_z, const double* z /* [n_z] complex128 */,
+                         double* G_out    /* [B][n_z][n_ops][n_ops] complex128 */,
+                         double* one_out  /* nullable, [B][n_ops] complex128 */,
+                         double* site_out /* nullable, [B][n_ops][n_ops] complex128 */);
 
 /* ---- one-shot host-buffer convenience (SURVEY 8(b) energy_batch / env_batch) ------------ */
 int qmps_energy_batch(qmps_ctx* ctx, int64_t B, const double* states, int kind, const double* h, int n_terms,

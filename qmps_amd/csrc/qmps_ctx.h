@@ -10,6 +10,7 @@
 //   qmps_capi_roto.hip       the rotosolve drivers of the energy and of the overlap objective
 //   qmps_capi_correlator.hip the two-point functions of the resident states
 //   qmps_capi_entanglement.hip the Schmidt spectra and entropies of the resident states
+//   qmps_capi_corrsum.hip   the correlator sums (structure factors) of the resident states
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>

@@ -452,5 +452,23 @@ struct EntanglementArgs {
   int64_t B;
 };
 hipError_t launch_entanglement(int D, const EntanglementArgs& a, hipStream_t st);
+// correlator sums of the resident states (qmps_corrsum.hip): one dense solve of order D^2 per (evaluation, z), one launch
+struct CorrSumArgs {
+  const void* A;       // [B][2][D][D] complex
+  const void* r;       // [B][D][D] complex right environments (any normalisation: everything is divided by tr r)
+  const void* ops;     // [n_ops][2][2] complex, O[t][s] = <t|O|s> (device)
+  const void* z;       // [n_z] complex (device)
+  void* G;             // [B][n_z][n_ops][n_ops] complex
+  void* one;           // nullable [B][n_ops] complex: <O_a>
+  void* site;          // nullable [B][n_ops][n_ops] complex: <O_a O_c> on one site
+  void* work;          // D = 16 only: n_slabs x correlator_sums_slab_bytes(), one matrix per workgroup
+  int64_t B;
+  int n_ops, n_z;      // 1 <= n_ops <= 4, n_z >= 1
+  int n_slabs;         // D = 16 only: workgroups of the fixed grid, 1 .. kCorrSumMaxSlabs
+};
+constexpr int kCorrSumMaxSlabs = 252;                     // 252 slabs of 1040 KiB stay below 256 MiB
+int64_t correlator_sums_slabs(int D, int64_t items);      // slabs the launch wants for this many (evaluation, z) items: 0 unless D = 16
+size_t correlator_sums_slab_bytes();
+hipError_t launch_correlator_sums(int D, const CorrSumArgs& a, hipStream_t st);
 
 }  // namespace qmps

@@ -275,6 +275,47 @@ class EnergyEngine:
                                            None if one is None else _f64(one.view(np.float64))))
         return (C, one) if want_one_site else C
 
+    def correlator_sums(self, ops, z, B=None, want_one_site=False, want_site=False):
+        """Sums over all distances of the connected two-point functions of the resident states (`launch` with the environments stored,
+        or `set_env_guess`; nothing is solved here): G[b, j, a, c] = sum_(n >= 1) z_j^n (<O_a(0) O_c(n)> - <O_a> <O_c>), shape
+        (B, n_z, m, m) complex128, by one linear solve of order D^2 per (b, j) - the resolvent of the transfer map with its fixed point
+        projected out, nothing truncated.  ops as in `correlators`; z: up to 1024 complex points with |z| <= 1.  want_one_site=True adds
+        one[b, a] = <O_a> (B, m), want_site=True adds site[b, a, c] = <O_a O_c> on one site (B, m, m), in this order after G.  A state
+        with a degenerate fixed point has no finite sum at |z| = 1: NaN for that (b, j) alone.  One kernel launch, one synchronisation."""
+        B = self.B if B is None else int(B)
+        ops = np.asarray(ops, dtype=np.complex128)
+        if ops.shape == (2, 2):
+            ops = ops[None]
+        if ops.ndim != 3 or ops.shape[1:] != (2, 2):
+            raise ValueError(f'ops: expected shape (m, 2, 2) or (2, 2), got {ops.shape}')
+        ops = np.ascontiguousarray(ops)
+        z = np.ascontiguousarray(np.asarray(z, dtype=np.complex128).reshape(-1))
+        m, n_z, n = ops.shape[0], z.shape[0], max(B, 0)
+        # (the library checks the sizes before anything is written: an array it refuses is never touched)
+        G = np.empty((B, n_z, m, m) if 0 <= n * n_z * m * m <= (1 << 26) else (0,), dtype=np.complex128)
+        one = np.empty((n, m), dtype=np.complex128) if want_one_site else None
+        site = np.empty((n, m, m), dtype=np.complex128) if want_site else None
+        L.check(self._lib.qmps_correlator_sums(self._ctx, B, m, _f64(ops.view(np.float64)), n_z, _f64(z.view(np.float64)), _f64(G.view(np.float64)),
+                                               None if one is None else _f64(one.view(np.float64)),
+                                               None if site is None else _f64(site.view(np.float64))))
+        out = (G,) + ((one,) if want_one_site else ()) + ((site,) if want_site else ())
+        return out if len(out) > 1 else G
+
+    def structure_factor(self, ops, k, B=None, want_one_site=False):
+        """Static structure factors of the resident states: S[b, q, a, c] = sum_(n = -inf .. inf) e^(-i k_q n) (<O_a(0) O_c(n)> - <O_a> <O_c>),
+        shape (B, n_k, m, m) complex128, k in radians per site (up to 512 values).  One call of `correlator_sums` at
+        z = (e^(-i k_0), e^(+i k_0), e^(-i k_1), ...) and the composition
+        S = site - one one + G_ac(e^(-ik)) + G_ca(e^(+ik)): the last term is the n < 0 half, <O_a(0) O_c(-n)> = <O_c(0) O_a(n)>.  For
+        Hermitian ops S[b, q] is a Hermitian, positive semi-definite matrix; S_zz(0) is the susceptibility.  want_one_site=True: returns
+        (S, one) with one[b, a] = <O_a>."""
+        k = np.asarray(k, dtype=np.float64).reshape(-1)
+        z = np.empty(2 * k.shape[0], dtype=np.complex128)
+        z[0::2] = np.exp(-1j * k)
+        z[1::2] = np.exp(1j * k)
+        G, one, site = self.correlator_sums(ops, z, B=B, want_one_site=True, want_site=True)
+        S = (site - one[:, :, None] * one[:, None, :])[:, None] + G[:, 0::2] + np.swapaxes(G[:, 1::2], -1, -2)
+        return (S, one) if want_one_site else S
+
     def entanglement(self, B=None, want_vectors=False):
         """Entanglement (Schmidt) spectra of the resident states from their resident environments (`launch` with the environments stored,
         or `set_env_guess`; nothing is solved here): p[b, k] = k-th largest eigenvalue of herm(r_b) / tr r_b, shape (B, D), descending and

@@ -461,3 +461,28 @@ def entanglement_entropy(params, D=2, state_tensor=ShallowCNOTStateTensor):
     eng.launch(K, max_iter=_GpuEnergyMixin.max_iter, tol=_GpuEnergyMixin.env_tol, solver='direct', store_env=True, krylov_fallback=D >= 8)
     p, S = eng.entanglement(B=K)
     return S, p, eng.results_status(K)
+
+
+def structure_factor(params, ops, k, D=2, state_tensor=ShallowCNOTStateTensor):
+    """Static structure factors of the states of K parameter rows - the companion of `ground_state_sweep` (params = out['params']) and
+    `correlation_functions`:
+      S (K, n_k, m, m)   S[., q, a, c] = sum_(n = -inf .. inf) e^(-i k_q n) (<O_a(0) O_c(n)> - <O_a> <O_c>); S_zz(0) is the susceptibility
+      one (K, m)         <O_a>
+      status (K,)        of the environment solve (STATUS_OK = 0; the structure factor of any other row is not to be trusted)
+    ops: (m, 2, 2) one-site operators (or one (2, 2) matrix), m <= 4; k: momenta in radians per site.  The tensors are built on the
+    device for the ansatz classes libqmps_hip knows (`device_kind`), one environment solve runs with the environments stored, and ONE
+    launch solves the deflated resolvent of the transfer map for every (state, k, sign): no chain is truncated, the cost does not
+    depend on the correlation length (`EnergyEngine.structure_factor`)."""
+    P = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float64)
+    K = P.shape[0]
+    kind = getattr(state_tensor, 'device_kind', None)
+    on_device = kind is not None and not (kind in (2, 6) and D != 2)
+    eng = _runtime.engine(D, K)
+    if on_device:
+        eng.set_ansatz_params(kind, P)
+    else:
+        eng.set_unitaries(np.stack([unitary(build_gate(state_tensor, D, p_)) for p_ in P]))
+    eng.set_hamiltonian(np.zeros((1, 4, 4), dtype=np.complex128))      # the launch wants a resident Hamiltonian: a single zero term
+    eng.launch(K, max_iter=_GpuEnergyMixin.max_iter, tol=_GpuEnergyMixin.env_tol, solver='direct', store_env=True, krylov_fallback=D >= 8)
+    S, one = eng.structure_factor(ops, k, B=K, want_one_site=True)
+    return S, one, eng.results_status(K)
