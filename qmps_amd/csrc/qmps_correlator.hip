@@ -12,21 +12,11 @@
 
 #include "qmps_kernels.h"
 #include "qmps_device.h"
-#include "qmps_complex.h"
+#include "qmps_observable.h"
 
 namespace qmps {
 
 namespace {
-
-constexpr int kMaxOps = 4;   // qmps_correlators refuses more: four operators span the one-site operators
-
-// 1 / t, NaN when t is zero or not finite (the documented answer of an evaluation without a usable environment)
-__device__ __forceinline__ double2 inv_trace(const double2 t) {
-  const double s = fmax(fabs(t.x), fabs(t.y));
-  if (!(s > 0.0) || !(s < INFINITY)) return make_double2(NAN, NAN);
-  const double u = t.x / s, v = t.y / s, n = (u * u + v * v) * s;
-  return make_double2(u / n, -v / n);
-}
 
 // ---- D = 2, 4: D consecutive lanes per evaluation, lane q owns row q of x -----------------------------------------------------
 // value of lane J of the own group of D lanes, in every lane of the group (DPP quad_perm)
@@ -46,10 +36,10 @@ constexpr int kRowTile = 8;   // steps gathered in LDS before they are stored: r
 template <int D>
 __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
   constexpr int EV = 64 / D;       // evaluations per workgroup (one wave)
-  __shared__ double2 sL[kMaxOps][D][64];             // L_a[i][q] of the lane that owns row q: [a][i][lane]
+  __shared__ double2 sL[kMaxObservableOps][D][64];             // L_a[i][q] of the lane that owns row q: [a][i][lane]
   __shared__ double2 sRow[2][D][64];                 // A_s[q][j] of the lane: [s][j][lane]
   __shared__ double2 sR[D][64];                      // r[q][j] of the lane, the start of every chain
-  __shared__ double2 sOut[EV][kMaxOps][kRowTile];
+  __shared__ double2 sOut[EV][kMaxObservableOps][kRowTile];
   const int lane = threadIdx.x, q = lane % D, e = lane / D;
   const int64_t b0 = (int64_t)blockIdx.x * EV;
   // lanes past the batch compute a copy of the last evaluation (every lane takes part in the DPP moves) and store nothing
@@ -112,7 +102,7 @@ __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
       dx = q == j ? rj.x : dx;
       dy = q == j ? rj.y : dy;
     }
-    inv = inv_trace(make_double2(group_sum<D>(dx), group_sum<D>(dy)));
+    inv = crecip(make_double2(group_sum<D>(dx), group_sum<D>(dy)));
   }
 
   // y_t = x A_t^+ (row q)
@@ -216,20 +206,20 @@ constexpr int kBlockTile = 16;   // steps gathered in LDS before they are stored
 
 // sums of cnt <= 8 values over the workgroup, results in every thread
 template <int D>
-__device__ __forceinline__ void block_sum_n(double (&v)[2 * kMaxOps], int cnt, double (*red)[2 * kMaxOps], int tid) {
+__device__ __forceinline__ void block_sum_n(double (&v)[2 * kMaxObservableOps], int cnt, double (*red)[2 * kMaxObservableOps], int tid) {
   constexpr int N = D * D;
 #pragma unroll
-  for (int u = 0; u < 2 * kMaxOps; ++u)
+  for (int u = 0; u < 2 * kMaxObservableOps; ++u)
     if (u < cnt) v[u] = wave_sum(v[u]);
   if (N > 64) {
     __syncthreads();
     if ((tid & 63) == 0) {
 #pragma unroll
-      for (int u = 0; u < 2 * kMaxOps; ++u) red[tid >> 6][u] = v[u];
+      for (int u = 0; u < 2 * kMaxObservableOps; ++u) red[tid >> 6][u] = v[u];
     }
     __syncthreads();
 #pragma unroll
-    for (int u = 0; u < 2 * kMaxOps; ++u) {
+    for (int u = 0; u < 2 * kMaxObservableOps; ++u) {
       double s = 0.0;
 #pragma unroll
       for (int w = 0; w < N / 64; ++w) s += red[w][u];
@@ -244,8 +234,8 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
   __shared__ double2 sA[2][D][P];
   __shared__ double2 sX[D][P];
   __shared__ double2 sZ[2][D][P];
-  __shared__ double sRed[NW][2 * kMaxOps];
-  __shared__ double2 sOut[kMaxOps][kBlockTile];
+  __shared__ double sRed[NW][2 * kMaxObservableOps];
+  __shared__ double2 sOut[kMaxObservableOps][kBlockTile];
   const int tid = threadIdx.x, i = tid / D, j = tid % D;
   const int64_t b = blockIdx.x;
   if (b >= p.B) return;
@@ -260,7 +250,7 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
   __syncthreads();
 
   // this thread's entry L_a[j][i] of every L_a: tr(L_a x) = sum_(i, j) L_a[j][i] x[i][j]
-  double2 Lji[kMaxOps];
+  double2 Lji[kMaxObservableOps];
   {
     double2 M[2][2];
 #pragma unroll
@@ -273,7 +263,7 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
         M[t][s] = m;
       }
 #pragma unroll
-    for (int a = 0; a < kMaxOps; ++a) {
+    for (int a = 0; a < kMaxObservableOps; ++a) {
       double2 l = make_double2(0.0, 0.0);
       if (a < n_ops) {
 #pragma unroll
@@ -284,13 +274,13 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
       Lji[a] = l;
     }
   }
-  double v[2 * kMaxOps];
+  double v[2 * kMaxObservableOps];
 #pragma unroll
-  for (int u = 0; u < 2 * kMaxOps; ++u) v[u] = 0.0;
+  for (int u = 0; u < 2 * kMaxObservableOps; ++u) v[u] = 0.0;
   v[0] = i == j ? r.x : 0.0;
   v[1] = i == j ? r.y : 0.0;
   block_sum_n<D>(v, 2, sRed, tid);
-  const double2 inv = inv_trace(make_double2(v[0], v[1]));
+  const double2 inv = crecip(make_double2(v[0], v[1]));
 
   // sum_(t, s) W[t][s] A_s x A_t^+ for the x in sX: z_t = sum_s W[t][s] A_s x through LDS, then z_t A_t^+
   auto apply = [&](const double2 w00, const double2 w01, const double2 w10, const double2 w11, const bool identity) {
@@ -322,7 +312,7 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
   // tr(L_a x) / tr r for every a, in every thread
   auto read_out = [&](const double2 x) {
 #pragma unroll
-    for (int a = 0; a < kMaxOps; ++a) {
+    for (int a = 0; a < kMaxObservableOps; ++a) {
       const double2 w = cmul(Lji[a], x);
       v[2 * a] = w.x;
       v[2 * a + 1] = w.y;
@@ -333,7 +323,7 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
   if (p.one != nullptr) {
     read_out(r);
 #pragma unroll
-    for (int a = 0; a < kMaxOps; ++a)
+    for (int a = 0; a < kMaxObservableOps; ++a)
       if (a < n_ops && tid == 0) ((double2*)p.one)[b * n_ops + a] = cmul(make_double2(v[2 * a], v[2 * a + 1]), inv);
   }
 
@@ -348,7 +338,7 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
       read_out(x);
       if (tid == 0) {
 #pragma unroll
-        for (int a = 0; a < kMaxOps; ++a)
+        for (int a = 0; a < kMaxObservableOps; ++a)
           if (a < n_ops) sOut[a][k] = cmul(make_double2(v[2 * a], v[2 * a + 1]), inv);
       }
       if (k == kBlockTile - 1 || n == n_max - 1) {
@@ -370,7 +360,7 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
 
 hipError_t launch_correlators(int D, const CorrelatorArgs& a, hipStream_t st) {
   if (a.B <= 0) return hipSuccess;
-  if (a.n_ops < 1 || a.n_ops > kMaxOps || a.n_max < 1) return hipErrorInvalidValue;
+  if (a.n_ops < 1 || a.n_ops > kMaxObservableOps || a.n_max < 1) return hipErrorInvalidValue;
   switch (D) {
     case 2: hipLaunchKernelGGL(correlator_rows_kernel<2>, dim3((unsigned)((a.B + 31) / 32)), dim3(64), 0, st, a); break;
     case 4: hipLaunchKernelGGL(correlator_rows_kernel<4>, dim3((unsigned)((a.B + 15) / 16)), dim3(64), 0, st, a); break;

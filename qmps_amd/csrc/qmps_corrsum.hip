@@ -30,21 +30,12 @@
 
 #include "qmps_kernels.h"
 #include "qmps_device.h"
-#include "qmps_complex.h"
+#include "qmps_observable.h"
 
 namespace qmps {
 
 namespace {
 
-constexpr int kMaxOps = 4;
-
-// 1 / t; NaN when t is zero or not finite
-__device__ __forceinline__ double2 crecip(const double2 t) {
-  const double s = fmax(fabs(t.x), fabs(t.y));
-  if (!(s > 0.0) || !(s < INFINITY)) return make_double2(NAN, NAN);
-  const double u = t.x / s, v = t.y / s, n = (u * u + v * v) * s;
-  return make_double2(u / n, -v / n);
-}
 // the size a pivot candidate is ranked by: |re| + |im|, infinite for a NaN (it is then chosen and marks the item)
 __device__ __forceinline__ double pivot_size(const double2 a) {
   const double v = fabs(a.x) + fabs(a.y);
@@ -372,7 +363,7 @@ struct BlockTiles {
   double2 r[D][P];
   double2 Y[2][D][P];
   double2 R[4][N];
-  double2 lv[kMaxOps][N];
+  double2 lv[kMaxObservableOps][N];
 };
 
 template <int D>
@@ -396,7 +387,7 @@ __device__ __forceinline__ void block_build(BlockTiles<D>& S, const double2* Ab,
 #pragma unroll
     for (int l = 0; l < D; ++l) cfma_conj(S.Y[s][i][l], S.A[t][j][l], v);
     S.R[ts][q] = v;
-    // (A_t^+ A_s)[j][i], parked in lv[ts] (kMaxOps == 4 slots) until the operators are applied below
+    // (A_t^+ A_s)[j][i], parked in lv[ts] (kMaxObservableOps == 4 slots) until the operators are applied below
 #pragma unroll
     for (int k = 0; k < D; ++k) cfma_cj(S.A[t][k][j], S.A[s][k][i], w);
     S.lv[ts][q] = w;
@@ -425,7 +416,7 @@ __device__ __forceinline__ void block_build(BlockTiles<D>& S, const double2* Ab,
 #pragma unroll
     for (int ts = 0; ts < 4; ++ts) w[ts >> 1][ts & 1] = S.lv[ts][q];
 #pragma unroll
-    for (int a = 0; a < kMaxOps; ++a) S.lv[a][q] = a < n_ops ? op_dot(O + 4 * a, w) : make_double2(0.0, 0.0);
+    for (int a = 0; a < kMaxObservableOps; ++a) S.lv[a][q] = a < n_ops ? op_dot(O + 4 * a, w) : make_double2(0.0, 0.0);
   }
   __syncthreads();
 }
@@ -453,7 +444,7 @@ __device__ __forceinline__ void store_one_site(const CorrSumArgs& p, int64_t b, 
 }
 
 __global__ __launch_bounds__(256) void corrsum_lds_kernel(CorrSumArgs p) {
-  constexpr int D = 8, N = 64, NC = N + kMaxOps;
+  constexpr int D = 8, N = 64, NC = N + kMaxObservableOps;
   __shared__ double2 sW[NC][N];          // column-major: sW[column][row]
   __shared__ BlockTiles<D> S;
   __shared__ double2 sPiv[NC];
@@ -516,7 +507,7 @@ __global__ __launch_bounds__(256) void corrsum_lds_kernel(CorrSumArgs p) {
   }
 }
 
-constexpr int kSlabColumns = 256 + kMaxOps;
+constexpr int kSlabColumns = 256 + kMaxObservableOps;
 constexpr size_t kSlabBytes = (size_t)kSlabColumns * 256 * sizeof(double2);
 
 __global__ __launch_bounds__(256) void corrsum_global_kernel(CorrSumArgs p) {
@@ -525,7 +516,7 @@ __global__ __launch_bounds__(256) void corrsum_global_kernel(CorrSumArgs p) {
   __shared__ double2 sPiv[kSlabColumns];
   __shared__ double sRedV[4];
   __shared__ int sRedI[4];
-  __shared__ double sSum[4][2 * kMaxOps * kMaxOps];
+  __shared__ double sSum[4][2 * kMaxObservableOps * kMaxObservableOps];
   const int tid = threadIdx.x, row = tid, i = row / D, j = row % D, wave = tid >> 6;
   const int m = p.n_ops, nc = N + m;
   const double2* O = (const double2*)p.ops;
@@ -633,7 +624,7 @@ size_t correlator_sums_slab_bytes() { return kSlabBytes; }
 
 hipError_t launch_correlator_sums(int D, const CorrSumArgs& a, hipStream_t st) {
   if (a.B <= 0) return hipSuccess;
-  if (a.n_ops < 1 || a.n_ops > kMaxOps || a.n_z < 1) return hipErrorInvalidValue;
+  if (a.n_ops < 1 || a.n_ops > kMaxObservableOps || a.n_z < 1) return hipErrorInvalidValue;
   const int64_t items = a.B * a.n_z;
   switch (D) {
     case 2:

@@ -8,9 +8,7 @@
 //   qmps_capi_overlap.hip    the time-evolution overlap objective and its gradient
 //   qmps_capi_evolve.hip     the BFGS evolve drivers
 //   qmps_capi_roto.hip       the rotosolve drivers of the energy and of the overlap objective
-//   qmps_capi_correlator.hip the two-point functions of the resident states
-//   qmps_capi_entanglement.hip the Schmidt spectra and entropies of the resident states
-//   qmps_capi_corrsum.hip   the correlator sums (structure factors) of the resident states
+//   qmps_capi_observables.hip  observables of the resident states: two-point functions, Schmidt spectra, correlator sums
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>

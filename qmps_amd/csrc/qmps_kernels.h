@@ -432,7 +432,11 @@ hipError_t launch_probe_copy(const void* src, void* dst, int64_t n16, hipStream_
 // copy of n8 x 8 bytes by a kernel on the given stream (pinned host memory <-> HBM without a copy-queue hop)
 hipError_t launch_stage_copy(const void* src, void* dst, int64_t n8, hipStream_t st);
 hipError_t launch_stage_copy2(const void* src1, void* dst1, int64_t n1, const void* src2, void* dst2, int64_t n2, hipStream_t st);
-// two-point functions of the resident states (qmps_correlator.hip): one launch for all n_ops^2 n_max values of every evaluation
+// ---- observables of the resident states (host: qmps_capi_observables.hip; device helpers shared by the kernels: qmps_observable.h) ----
+// operators per call of qmps_correlators / qmps_correlator_sums: four span the one-site operators.  The host refuses more, the kernels
+// size their LDS tiles and registers by it
+constexpr int kMaxObservableOps = 4;
+// two-point functions (qmps_correlator.hip): one launch for all n_ops^2 n_max values of every evaluation
 struct CorrelatorArgs {
   const void* A;       // [B][2][D][D] complex
   const void* r;       // [B][D][D] complex right environments (any normalisation: the results are divided by tr r)
@@ -440,10 +444,10 @@ struct CorrelatorArgs {
   void* C;             // [B][n_ops][n_ops][n_max] complex: <O_a(site 0) O_c(site n)>, n = 1 .. n_max
   void* one;           // nullable [B][n_ops] complex: <O_a>
   int64_t B;
-  int n_ops, n_max;    // 1 <= n_ops <= 4, n_max >= 1
+  int n_ops, n_max;    // 1 <= n_ops <= kMaxObservableOps, n_max >= 1
 };
 hipError_t launch_correlators(int D, const CorrelatorArgs& a, hipStream_t st);
-// Schmidt spectra of the resident states (qmps_entanglement.hip): batched complex-Hermitian Jacobi, one launch
+// Schmidt spectra (qmps_entanglement.hip): batched complex-Hermitian Jacobi, one launch
 struct EntanglementArgs {
   const void* r;       // [B][D][D] complex right environments (herm(r) / tr r is diagonalised)
   double* p;           // [B][D] eigenvalues, descending
@@ -452,7 +456,7 @@ struct EntanglementArgs {
   int64_t B;
 };
 hipError_t launch_entanglement(int D, const EntanglementArgs& a, hipStream_t st);
-// correlator sums of the resident states (qmps_corrsum.hip): one dense solve of order D^2 per (evaluation, z), one launch
+// correlator sums (qmps_corrsum.hip): one dense solve of order D^2 per (evaluation, z), one launch
 struct CorrSumArgs {
   const void* A;       // [B][2][D][D] complex
   const void* r;       // [B][D][D] complex right environments (any normalisation: everything is divided by tr r)
@@ -463,7 +467,7 @@ struct CorrSumArgs {
   void* site;          // nullable [B][n_ops][n_ops] complex: <O_a O_c> on one site
   void* work;          // D = 16 only: n_slabs x correlator_sums_slab_bytes(), one matrix per workgroup
   int64_t B;
-  int n_ops, n_z;      // 1 <= n_ops <= 4, n_z >= 1
+  int n_ops, n_z;      // 1 <= n_ops <= kMaxObservableOps, n_z >= 1
   int n_slabs;         // D = 16 only: workgroups of the fixed grid, 1 .. kCorrSumMaxSlabs
 };
 constexpr int kCorrSumMaxSlabs = 252;                     // 252 slabs of 1040 KiB stay below 256 MiB

@@ -30,6 +30,16 @@ def _c128(a, shape_tail, name):
     return a
 
 
+def _one_site_ops(ops):
+    """(m, 2, 2) array-like or one (2, 2) matrix -> contiguous (m, 2, 2) complex128"""
+    ops = np.asarray(ops, dtype=np.complex128)
+    if ops.shape == (2, 2):
+        ops = ops[None]
+    if ops.ndim != 3 or ops.shape[1:] != (2, 2):
+        raise ValueError(f'ops: expected shape (m, 2, 2) or (2, 2), got {ops.shape}')
+    return np.ascontiguousarray(ops)
+
+
 class EnergyEngine:
     """Owns one `qmps_ctx`.  Not thread-safe; one engine per thread / device."""
 
@@ -260,12 +270,7 @@ class EnergyEngine:
         (B, m, m, n_max) complex128.  ops: (m, 2, 2) array-like or one (2, 2) matrix, O[t, s] = <t|O|s>, 1 <= m <= 4, need not be
         Hermitian.  want_one_site=True: returns (C, one) with one[b, a] = <O_a>, shape (B, m).  One kernel launch, one synchronisation."""
         B = self.B if B is None else int(B)
-        ops = np.asarray(ops, dtype=np.complex128)
-        if ops.shape == (2, 2):
-            ops = ops[None]
-        if ops.ndim != 3 or ops.shape[1:] != (2, 2):
-            raise ValueError(f'ops: expected shape (m, 2, 2) or (2, 2), got {ops.shape}')
-        ops = np.ascontiguousarray(ops)
+        ops = _one_site_ops(ops)
         m, n_max = ops.shape[0], int(n_max)
         size = max(B, 0) * m * m * max(n_max, 0)
         # (the library checks the sizes before anything is written: an array it refuses is never touched)
@@ -283,12 +288,7 @@ class EnergyEngine:
         one[b, a] = <O_a> (B, m), want_site=True adds site[b, a, c] = <O_a O_c> on one site (B, m, m), in this order after G.  A state
         with a degenerate fixed point has no finite sum at |z| = 1: NaN for that (b, j) alone.  One kernel launch, one synchronisation."""
         B = self.B if B is None else int(B)
-        ops = np.asarray(ops, dtype=np.complex128)
-        if ops.shape == (2, 2):
-            ops = ops[None]
-        if ops.ndim != 3 or ops.shape[1:] != (2, 2):
-            raise ValueError(f'ops: expected shape (m, 2, 2) or (2, 2), got {ops.shape}')
-        ops = np.ascontiguousarray(ops)
+        ops = _one_site_ops(ops)
         z = np.ascontiguousarray(np.asarray(z, dtype=np.complex128).reshape(-1))
         m, n_z, n = ops.shape[0], z.shape[0], max(B, 0)
         # (the library checks the sizes before anything is written: an array it refuses is never touched)

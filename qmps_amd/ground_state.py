@@ -413,14 +413,9 @@ def ground_state_sweep(terms, coefficients, D=2, depth=2, state_tensor=ShallowCN
     return out
 
 
-def correlation_functions(params, ops, n_max, D=2, state_tensor=ShallowCNOTStateTensor, connected=False):
-    """Two-point functions of the states of K parameter rows - the companion of `ground_state_sweep` (params = out['params']):
-      C (K, m, m, n_max)   C[k, a, c, n - 1] = <O_a(site 0) O_c(site n)>, n = 1 .. n_max  (connected=True: minus <O_a> <O_c>)
-      one (K, m)           <O_a>
-      status (K,)          of the environment solve (STATUS_OK = 0; the correlators of any other row are not to be trusted)
-    ops: (m, 2, 2) one-site operators (or one (2, 2) matrix), m <= 4, not necessarily Hermitian.  The tensors are built on the device for
-    the ansatz classes libqmps_hip knows (`device_kind`), one environment solve runs with the environments stored, and ONE launch of the
-    correlator kernel walks the n_max transfer-map applications of every (state, operator) chain."""
+def _resident_states(params, D, state_tensor):
+    """The shared opening of the observables below: the states of the K parameter rows and their environments made resident by one
+    direct solve.  Returns (engine, K); `engine.results_status(K)` is the status of that solve."""
     P = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float64)
     K = P.shape[0]
     kind = getattr(state_tensor, 'device_kind', None)
@@ -432,6 +427,18 @@ def correlation_functions(params, ops, n_max, D=2, state_tensor=ShallowCNOTState
         eng.set_unitaries(np.stack([unitary(build_gate(state_tensor, D, p_)) for p_ in P]))
     eng.set_hamiltonian(np.zeros((1, 4, 4), dtype=np.complex128))      # the launch wants a resident Hamiltonian: a single zero term
     eng.launch(K, max_iter=_GpuEnergyMixin.max_iter, tol=_GpuEnergyMixin.env_tol, solver='direct', store_env=True, krylov_fallback=D >= 8)
+    return eng, K
+
+
+def correlation_functions(params, ops, n_max, D=2, state_tensor=ShallowCNOTStateTensor, connected=False):
+    """Two-point functions of the states of K parameter rows - the companion of `ground_state_sweep` (params = out['params']):
+      C (K, m, m, n_max)   C[k, a, c, n - 1] = <O_a(site 0) O_c(site n)>, n = 1 .. n_max  (connected=True: minus <O_a> <O_c>)
+      one (K, m)           <O_a>
+      status (K,)          of the environment solve (STATUS_OK = 0; the correlators of any other row are not to be trusted)
+    ops: (m, 2, 2) one-site operators (or one (2, 2) matrix), m <= 4, not necessarily Hermitian.  The tensors are built on the device for
+    the ansatz classes libqmps_hip knows (`device_kind`), one environment solve runs with the environments stored, and ONE launch of the
+    correlator kernel walks the n_max transfer-map applications of every (state, operator) chain."""
+    eng, K = _resident_states(params, D, state_tensor)
     C, one = eng.correlators(ops, n_max, B=K, want_one_site=True)
     status = eng.results_status(K)
     if connected:
@@ -448,17 +455,7 @@ def entanglement_entropy(params, D=2, state_tensor=ShallowCNOTStateTensor):
     The tensors are built on the device for the ansatz classes libqmps_hip knows (`device_kind`), one environment solve runs with the
     environments stored, and ONE launch of the Jacobi kernel diagonalises them where they are (`EnergyEngine.entanglement`).  Renyi
     entropies are one line on p: ln(sum p^a) / (1 - a)."""
-    P = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float64)
-    K = P.shape[0]
-    kind = getattr(state_tensor, 'device_kind', None)
-    on_device = kind is not None and not (kind in (2, 6) and D != 2)
-    eng = _runtime.engine(D, K)
-    if on_device:
-        eng.set_ansatz_params(kind, P)
-    else:
-        eng.set_unitaries(np.stack([unitary(build_gate(state_tensor, D, p_)) for p_ in P]))
-    eng.set_hamiltonian(np.zeros((1, 4, 4), dtype=np.complex128))      # the launch wants a resident Hamiltonian: a single zero term
-    eng.launch(K, max_iter=_GpuEnergyMixin.max_iter, tol=_GpuEnergyMixin.env_tol, solver='direct', store_env=True, krylov_fallback=D >= 8)
+    eng, K = _resident_states(params, D, state_tensor)
     p, S = eng.entanglement(B=K)
     return S, p, eng.results_status(K)
 
@@ -473,16 +470,6 @@ def structure_factor(params, ops, k, D=2, state_tensor=ShallowCNOTStateTensor):
     device for the ansatz classes libqmps_hip knows (`device_kind`), one environment solve runs with the environments stored, and ONE
     launch solves the deflated resolvent of the transfer map for every (state, k, sign): no chain is truncated, the cost does not
     depend on the correlation length (`EnergyEngine.structure_factor`)."""
-    P = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float64)
-    K = P.shape[0]
-    kind = getattr(state_tensor, 'device_kind', None)
-    on_device = kind is not None and not (kind in (2, 6) and D != 2)
-    eng = _runtime.engine(D, K)
-    if on_device:
-        eng.set_ansatz_params(kind, P)
-    else:
-        eng.set_unitaries(np.stack([unitary(build_gate(state_tensor, D, p_)) for p_ in P]))
-    eng.set_hamiltonian(np.zeros((1, 4, 4), dtype=np.complex128))      # the launch wants a resident Hamiltonian: a single zero term
-    eng.launch(K, max_iter=_GpuEnergyMixin.max_iter, tol=_GpuEnergyMixin.env_tol, solver='direct', store_env=True, krylov_fallback=D >= 8)
+    eng, K = _resident_states(params, D, state_tensor)
     S, one = eng.structure_factor(ops, k, B=K, want_one_site=True)
     return S, one, eng.results_status(K)

@@ -2,55 +2,21 @@
 tests/correlator_cases.py evaluated from the tensors and environments read back from the device (the kernel alone, within the
 rounding bound), against the oracle's own environments and state vectors (1e-10, the tolerance the energy tests hold against the
 dense-eig oracle), and the contract of the call: conventions, window, fused-ansatz batches, untouched state, argument errors."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import correlator_cases as K
+import resident_cases as RS
 from oracle import qmps_oracle as O
 from qmps_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-H_TFIM = O.hamiltonian_matrix({'ZZ': -1, 'X': 1})
-_dp = ctypes.POINTER(ctypes.c_double)
-_SOLVED = {}
-
-
-def _solve(eng, A, D):
-    eng.set_tensors(A)
-    eng.set_hamiltonian(H_TFIM)
-    eng.launch(A.shape[0], solver='direct', store_env=True, krylov_fallback=(D == 8))
-
-
-def _haar(engine_factory, D):
-    """Engine with the Haar batch and its solved environments resident; (A, r, status) as read back.  Solved once per bond dimension:
-    later calls put the very same arrays back (qmps_set_env_guess copies verbatim), so one reference serves every test."""
-    eng = engine_factory(D)
-    if D not in _SOLVED:
-        _solve(eng, K.haar_tensors(D), D)
-        st = eng.results(K.HAAR_B)[2]
-        A, r = eng.tensors(K.HAAR_B), eng.environments(K.HAAR_B)
-        assert np.array_equal(A, K.haar_tensors(D))
-        for a in (A, r, st):
-            a.setflags(write=False)
-        _SOLVED[D] = {'A': A, 'r': r, 'st': st, 'ref': {}}
-    else:
-        eng.set_tensors(_SOLVED[D]['A'])
-        eng.set_hamiltonian(H_TFIM)
-        eng.set_env_guess(_SOLVED[D]['r'])
-    return eng, _SOLVED[D]
-
-
 def _reference(D, ops_name, rows, n_max):
     """Long-double reference from the read-back arrays, cached per (operators, block of the plan)."""
-    s = _SOLVED[D]
-    key = (ops_name, rows, n_max)
-    if key not in s['ref']:
-        ops = {'generic': K.generic_ops(), 'paulis': K.PAULIS}[ops_name]
-        s['ref'][key] = K.reference(s['A'][:rows], s['r'][:rows], ops, n_max)
-    return s['ref'][key]
+    s = RS.solved(D)
+    ops = {'generic': K.generic_ops(), 'paulis': K.PAULIS}[ops_name]
+    return RS.cached(D, __name__, (ops_name, rows, n_max), lambda: K.reference(s['A'][:rows], s['r'][:rows], ops, n_max))
 
 
 @pytest.mark.parametrize('D', K.DS)
@@ -58,7 +24,7 @@ def test_kernel_alone_within_the_rounding_bound(engine_factory, D):
     """Haar tensors, environments stored, tensors and environments read back; `correlators` against the long-double reference of
     those arrays, elementwise within bound(D, n): B in (1, 17, 65, 130) x n_ops in (1, 3, 4) x n_max in (1, 2, 7), n_max = 64 at
     B = 1 and 17, n_max = 512 at D = 2, 4 (B = 17); non-Hermitian complex operators."""
-    eng, s = _haar(engine_factory, D)
+    eng, s = RS.haar(engine_factory, D)
     (rows_s, n_s), (rows_l, n_l) = K.reference_plan(D)
     worst, worst_ratio, worst_one = 0.0, 0.0, 0.0
     for B, m, n_max in K.kernel_cases(D):
@@ -78,7 +44,7 @@ def test_against_the_state_vectors_of_the_oracle(engine_factory):
     """D = 2, B = 8, n <= 5: the oracle's state-vector route with its own get_env_exact - no transfer map, no device environment."""
     eng = engine_factory(2)
     U = O.haar_unitaries(np.random.default_rng(5402), 4, 8)
-    _solve(eng, O.unitary_to_tensor(U), 2)
+    RS.solve(eng, O.unitary_to_tensor(U), 2)
     ops = np.concatenate([K.generic_ops()[:2], K.SIGMA_PLUS[None]])
     C, one = eng.correlators(ops, 5, B=8, want_one_site=True)
     assert np.all(eng.results_status(8) == 0)
@@ -90,7 +56,7 @@ def test_against_the_state_vectors_of_the_oracle(engine_factory):
 @pytest.mark.parametrize('D', K.DS)
 def test_against_the_dense_eig_environment(engine_factory, D):
     """The reference evaluated with env_dense_eig's r instead of the device's: every Haar item has status 0."""
-    eng, s = _haar(engine_factory, D)
+    eng, s = RS.haar(engine_factory, D)
     assert np.all(s['st'] == 0)
     rows = 12 if D < 16 else 6
     ops = np.concatenate([K.generic_ops()[:3], K.SIGMA_PLUS[None]])
@@ -104,7 +70,7 @@ def test_against_the_dense_eig_environment(engine_factory, D):
 
 @pytest.mark.parametrize('D', K.DS)
 def test_conventions_with_the_paulis(engine_factory, D):
-    eng, s = _haar(engine_factory, D)
+    eng, s = RS.haar(engine_factory, D)
     B = 17
     C, one = eng.correlators(K.PAULIS, 7, B=B, want_one_site=True)
     assert np.abs(C[:, 0, :, :] - one[:, :, None]).max() < 1e-10          # identity on site 0: <O_c>
@@ -125,7 +91,7 @@ def test_fused_ansatz_batch(engine_factory):
     P = K.ansatz_params(4)
     R = P.shape[0]
     ops = np.stack([K.SIGMA_PLUS, K.Z, K.X])
-    eng.set_hamiltonian(H_TFIM)
+    eng.set_hamiltonian(RS.H_TFIM)
     eng.set_ansatz_params(_lib.ANSATZ_SHALLOW_CNOT, P)
     eng.launch(R, solver='direct', store_env=True)
     C, one = eng.correlators(ops, K.N_LONG, B=R, want_one_site=True)
@@ -144,7 +110,7 @@ def test_fused_ansatz_batch(engine_factory):
 
 @pytest.mark.parametrize('D', K.DS)
 def test_window(engine_factory, D):
-    eng, s = _haar(engine_factory, D)
+    eng, s = RS.haar(engine_factory, D)
     ops = K.generic_ops()[:3]
     full, one_full = eng.correlators(ops, 7, B=K.HAAR_B, want_one_site=True)
     eng.set_window(64)
@@ -157,7 +123,7 @@ def test_window(engine_factory, D):
 def test_nothing_else_moves(engine_factory, D):
     eng = engine_factory(D)
     B = 65
-    _solve(eng, K.haar_tensors(D)[:B], D)
+    RS.solve(eng, K.haar_tensors(D)[:B], D)
     before = (eng.results(B), eng.environments(B), eng.results_status(B), eng.tensors(B))
     eng.correlators(K.generic_ops(), 7, B=B, want_one_site=True)
     after = (eng.results(B), eng.environments(B), eng.results_status(B), eng.tensors(B))
@@ -166,11 +132,11 @@ def test_nothing_else_moves(engine_factory, D):
 
 
 def test_argument_errors(engine_factory):
-    eng, s = _haar(engine_factory, 4)
+    eng, s = RS.haar(engine_factory, 4)
     lib, ctx = eng._lib, eng._ctx
     ops = np.ascontiguousarray(K.PAULIS).view(np.float64)
     out = np.full(2 * 17 * 16 * 4, 7.0)
-    f = lambda a: a.ctypes.data_as(_dp)
+    f = lambda a: a.ctypes.data_as(RS.DP)
 
     def refused(rc, word):
         msg = lib.qmps_last_error().decode()

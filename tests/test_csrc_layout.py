@@ -7,7 +7,7 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'qmps_amd', 'csrc')
 
-SHARED_HELPERS = ('cmul', 'cmulc', 'cfma', 'cfms', 'cfma_conj', 'cfma_cj', 'cmma16', 'cmma16_3m', 'swz32', 'rx_lanes')
+SHARED_HELPERS = ('cmul', 'cmulc', 'cfma', 'cfms', 'cfma_conj', 'cfma_cj', 'cmma16', 'cmma16_3m', 'swz32', 'rx_lanes', 'crecip')
 
 
 def sources():

@@ -2,20 +2,17 @@
 reference of tests/entanglement_cases.py (the kernels alone: the cases go in verbatim through qmps_set_env_guess), against the
 oracle's dense-eig environments after a real solve, and the contract of the call: NaN rows, window, fused-ansatz batches, untouched
 state, argument errors, the host helper."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import entanglement_cases as K
+import resident_cases as RS
 from oracle import qmps_oracle as O
 from qmps_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-H_TFIM = O.hamiltonian_matrix({'ZZ': -1, 'X': 1})
 SOLVE_TOL = 1e-13                     # EnergyEngine.launch's default tolerance of the environment solve
-_dp = ctypes.POINTER(ctypes.c_double)
 _HAAR = {}
 
 
@@ -78,9 +75,7 @@ def test_after_a_real_solve(engine_factory, D):
     Cholesky test found."""
     B = 12 if D < 16 else 6
     eng = engine_factory(D)
-    eng.set_tensors(_haar(D, B))
-    eng.set_hamiltonian(H_TFIM)
-    eng.launch(B, store_env=True, krylov_fallback=(D == 8))
+    RS.solve(eng, _haar(D, B), D)
     p, S, V = eng.entanglement(B=B, want_vectors=True)
     st = eng.results_status(B)
     ref = np.stack([np.linalg.eigvalsh(O.env_dense_eig(a)[1])[::-1] for a in _haar(D, B)])
@@ -124,9 +119,7 @@ def test_embedded_tensor_keeps_the_spectrum(engine_factory):
     ph = np.einsum('bsij,bsij->b', ref.conj(), A4)
     assert np.abs(A4 - (ph / np.abs(ph))[:, None, None, None] * ref).max() < 1e-10
     e2 = engine_factory(2)
-    e2.set_tensors(A2)
-    e2.set_hamiltonian(H_TFIM)
-    e2.launch(B, store_env=True)
+    RS.solve(e2, A2, 2)
     assert np.all(e2.results_status(B) == 0)
     r2 = e2.environments(B)
     p2, S2 = e2.entanglement(B=B)
@@ -149,7 +142,7 @@ def test_fused_ansatz_batch(engine_factory):
     eng = engine_factory(4)
     P = np.random.default_rng(6204).standard_normal((21, 4))
     R = P.shape[0]
-    eng.set_hamiltonian(H_TFIM)
+    eng.set_hamiltonian(RS.H_TFIM)
     eng.set_ansatz_params(_lib.ANSATZ_SHALLOW_CNOT, P)
     eng.launch(R, solver='direct', store_env=True)
     p, S, V = eng.entanglement(B=R, want_vectors=True)
@@ -186,9 +179,7 @@ def test_window(engine_factory, D):
 def test_nothing_else_moves(engine_factory, D):
     eng = engine_factory(D)
     B = 65
-    eng.set_tensors(_haar(D, B))
-    eng.set_hamiltonian(H_TFIM)
-    eng.launch(B, solver='direct', store_env=True, krylov_fallback=(D == 8))
+    RS.solve(eng, _haar(D, B), D)
     before = (eng.results(B), eng.environments(B), eng.results_status(B), eng.tensors(B))
     eng.entanglement(B=B, want_vectors=True)
     eng.entanglement(B=B)
@@ -201,7 +192,7 @@ def test_argument_errors(engine_factory):
     eng = _resident_cases(engine_factory, 4, 40)
     lib, ctx = eng._lib, eng._ctx
     out = np.full(4 * 64, 7.0)
-    f = lambda a: a.ctypes.data_as(_dp)
+    f = lambda a: a.ctypes.data_as(RS.DP)
 
     def refused(rc, code, word):
         msg = lib.qmps_last_error().decode()

@@ -5,60 +5,34 @@ the host composition of the structure factor, and the contract of the call: wind
 errors, degenerate fixed points and unusable environments.
 
 Worst err / bound of the kernel-alone comparison measured on an MI355X: see profiles/EXPERIMENTS.md."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import correlator_cases as K
+import resident_cases as RS
 import structure_factor_cases as S
 from oracle import qmps_oracle as O
 from qmps_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-H_TFIM = O.hamiltonian_matrix({'ZZ': -1, 'X': 1})
-_dp = ctypes.POINTER(ctypes.c_double)
-_SOLVED = {}
 D16_ROWS = max(S.D16_BATCHES)
 D16_Z = S.Z[:max(S.D16_N_Z)]
 
 
-def _solve(eng, A, D):
-    eng.set_tensors(A)
-    eng.set_hamiltonian(H_TFIM)
-    eng.launch(A.shape[0], solver='direct', store_env=True, krylov_fallback=(D == 8))
-
-
 def _haar(engine_factory, D):
-    """Engine with the Haar batch and its solved environments resident; solved once per bond dimension: later calls put the very same
-    arrays back (qmps_set_env_guess copies verbatim), so one reference serves every test."""
-    eng = engine_factory(D)
-    if D not in _SOLVED:
-        _solve(eng, K.haar_tensors(D), D)
-        st = eng.results(K.HAAR_B)[2]
-        A, r = eng.tensors(K.HAAR_B), eng.environments(K.HAAR_B)
-        assert np.array_equal(A, K.haar_tensors(D)) and np.all(st == 0)
-        for a in (A, r):
-            a.setflags(write=False)
-        _SOLVED[D] = {'A': A, 'r': r, 'ref': {}}
-    else:
-        eng.set_tensors(_SOLVED[D]['A'])
-        eng.set_hamiltonian(H_TFIM)
-        eng.set_env_guess(_SOLVED[D]['r'])
-    return eng, _SOLVED[D]
+    eng, s = RS.haar(engine_factory, D)
+    assert np.all(s['st'] == 0)
+    return eng, s
 
 
 def _cached(D, key, make):
-    ref = _SOLVED[D]['ref']
-    if key not in ref:
-        ref[key] = make()
-    return ref[key]
+    return RS.cached(D, __name__, key, make)
 
 
 def _haar_reference(D):
     """(G, one, site, bound) of the generic operators on the rows and points the kernel comparison uses, from the read-back arrays."""
-    s = _SOLVED[D]
+    s = RS.solved(D)
     rows, z = (K.HAAR_B, S.Z) if D <= 8 else (D16_ROWS, D16_Z)
     return _cached(D, 'haar', lambda: S.reference(s['A'][:rows], s['r'][:rows], K.generic_ops(), z) + (S.bound(s['A'][:rows], s['r'][:rows], z),))
 
@@ -174,7 +148,7 @@ def test_fused_ansatz_batch(engine_factory, D):
     R = P.shape[0]
     ops = np.stack([K.SIGMA_PLUS, K.Z, K.X])
     z = S.Z[2:5]
-    eng.set_hamiltonian(H_TFIM)
+    eng.set_hamiltonian(RS.H_TFIM)
     eng.set_ansatz_params(_lib.ANSATZ_SHALLOW_CNOT, P)
     eng.launch(R, solver='direct', store_env=True)
     G, one, site = eng.correlator_sums(ops, z, B=R, want_one_site=True, want_site=True)
@@ -195,7 +169,7 @@ def test_fused_ansatz_batch(engine_factory, D):
 def test_nothing_else_moves(engine_factory, D):
     eng = engine_factory(D)
     B = 65
-    _solve(eng, K.haar_tensors(D)[:B], D)
+    RS.solve(eng, K.haar_tensors(D)[:B], D)
     before = (eng.results(B), eng.environments(B), eng.results_status(B), eng.tensors(B))
     eng.correlator_sums(K.generic_ops(), S.Z[:2], B=B, want_one_site=True, want_site=True)
     eng.structure_factor(K.Z, [0.0, 0.3], B=B)
@@ -212,7 +186,7 @@ def test_argument_errors(engine_factory):
     out = np.full(2 * 17 * 6 * 16, 7.0)
     one = np.full(2 * 17 * 4, 7.0)
     site = np.full(2 * 17 * 16, 7.0)
-    f = lambda a: a.ctypes.data_as(_dp)
+    f = lambda a: a.ctypes.data_as(RS.DP)
 
     def untouched():
         return np.all(out == 7.0) and np.all(one == 7.0) and np.all(site == 7.0)
