@@ -10,7 +10,7 @@
 //     into LDS (rows padded to 17);
 //   * the RIGHT and the LEFT fixed point of the iterate's mixed transfer map by the power method on the matrix cores
 //     (v_mfma_f64_16x16x4, three-product complex form): waves 0-3 the map, waves 4-7 the adjoint map, wave w of a team owns the
-//     physical index s = w exactly as in overlap_mfma_d16x4_body (qmps_overlap.hip); each team runs at its own pace on a barrier of
+//     physical index s = w exactly as in overlap_mfma_d16x4_body (qmps_overlap_d16.hip; the steps: qmps_tile16.h); each team runs at its own pace on a barrier of
 //     its own (an arrival counter in LDS: team_barrier) and waits for the other at the workgroup barrier behind the solves;
 //   * G_s = y^+ C_s r from the right team's registers (C_s is still there in the A-layout, r in the accumulator layout IS the
 //     B-layout): two products per wave;
@@ -35,6 +35,7 @@
 #include "qmps_kernels.h"
 #include "qmps_device.h"
 #include "qmps_complex.h"
+#include "qmps_tile16.h"
 #include "qmps_circuit_wave.h"
 #include "qmps_evolve_core.h"
 
@@ -42,7 +43,7 @@ namespace qmps {
 
 namespace {
 constexpr int kW16 = 8;                      // waves per workgroup: two teams of four
-constexpr int kLdp = 17;                     // padded row of a tensor / transpose tile in LDS
+constexpr int kLdp = kTile16Ld;              // padded row of a tensor / transpose tile in LDS
 constexpr int kTens = 2 * 16 * kLdp;         // a tensor [s][i][j]
 constexpr int kScrT = kW16 * 16 * kLdp;      // the waves' private transpose tiles
 constexpr int kScrX = kScrT + 2 * kW16 * 256;    // + two sets of one exchange matrix per wave
@@ -69,106 +70,17 @@ __device__ __forceinline__ void team_barrier(int* cnt, int target) {
 // - Bt this team's candidate tensor - or, with adj, its adjoint, from the start vector xs (row-major [16][16] in LDS; null or zero:
 // the identity) to a residual of sqrt(tol2) or max_rounds steps.  enabled = false: the team sets up and skips the iteration.
 // The two workgroup barriers of the set-up are the only ones: the caller joins the teams again behind the call.
-// The loop is overlap_mfma_d16x4_body's (qmps_overlap.hip) without deflation steps and without the Krylov hand-over.
+// Set-up, start vector and convergence test are overlap_mfma_d16x4_body's (qmps_tile16.h); the loop has no deflation steps and no Krylov hand-over.
 __device__ __forceinline__ void solve_teams_d16(const double2* sA, const double2* Bt, bool adj, bool enabled, const double2* W, const double2* xs, double tol2,
                                                 int max_rounds, double2 (*sT_all)[16 * kLdp], double2 (*sX_all)[256], int* sArrive, Solve16& o) {
-  constexpr int D = 16, LD = kLdp;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15, team = wave >> 2, tw = wave & 3;
+  const int wave = threadIdx.x >> 6, team = wave >> 2, tw = wave & 3;
   double2* sT = sT_all[wave];
-  auto to_a_layout = [&](const v4f64& re, const v4f64& im, double (&are)[4], double (&aim)[4]) {
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sT[(4 * q + g) * LD + c] = make_double2(re[q], im[q]);
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const double2 t = sT[c * LD + 4 * kk + g];
-      are[kk] = t.x;
-      aim[kk] = t.y;
-    }
-  };
-  const int t1 = tw >> 1, t2 = tw & 1;          // this wave's pair (s = 2 t1 + t2 = tw)
   double bre[4], bimn[4];                       // conj(Bm_w) in A-layout == Bm_w^+ in B-layout (adjoint: Bm_w in B-layout)
-  {
-    double pa[4], pai[4], pb[4], pbi[4];
-    v4f64 qa, qai, qb, qbi;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const double2 va = sA[(t1 * D + c) * LD + 4 * kk + g], vb = Bt[(t1 * D + c) * LD + 4 * kk + g];
-      pa[kk] = va.x; pai[kk] = va.y;
-      pb[kk] = vb.x; pbi[kk] = vb.y;
-      const double2 wa = sA[(t2 * D + 4 * kk + g) * LD + c], wb = Bt[(t2 * D + 4 * kk + g) * LD + c];
-      qa[kk] = wa.x; qai[kk] = wa.y;
-      qb[kk] = wb.x; qbi[kk] = wb.y;
-    }
-    v4f64 zr = {0, 0, 0, 0}, zi = {0, 0, 0, 0};
-    cmma16(pa, pai, qa, qai, zr, zi);           // AA_w = A_t1 A_t2
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sX_all[wave][q * 64 + lane] = make_double2(zr[q], zi[q]);
-    v4f64 yr = {0, 0, 0, 0}, yi = {0, 0, 0, 0};
-    cmma16(pb, pbi, qb, qbi, yr, yi);           // Bm_w = B_t1 B_t2
-    if (adj) {
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        bre[kk] = yr[kk];
-        bimn[kk] = yi[kk];
-      }
-    } else {
-      double tr[4], ti[4];
-      to_a_layout(yr, yi, tr, ti);
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        bre[kk] = tr[kk];
-        bimn[kk] = -ti[kk];
-      }
-    }
-    if (threadIdx.x < 2) sArrive[threadIdx.x] = 0;
-    __syncthreads();
-    v4f64 sr = {0, 0, 0, 0}, si = {0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const double2 w = W[tw * 4 + t];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const double2 v = sX_all[team * 4 + t][q * 64 + lane];
-        sr[q] += w.x * v.x - w.y * v.y;
-        si[q] += w.x * v.y + w.y * v.x;
-      }
-    }
-    if (adj) {                                  // C_w^+ in A-layout = conj of C_w in the accumulator layout
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        o.cre[kk] = sr[kk];
-        o.cim[kk] = -si[kk];
-      }
-    } else {
-      to_a_layout(sr, si, o.cre, o.cim);
-    }
-    __syncthreads();                            // the exchange buffers are free again; the arrival counters are reset
-  }
+  if (threadIdx.x < 2) sArrive[threadIdx.x] = 0;      // (the arrival counters: reset under the set-up's barriers)
+  tile16_split_setup(sA, Bt, kLdp, W, tw, adj, sT, sX_all + team * 4, o.cre, o.cim, bre, bimn);
   v4f64 xr, xi;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const double2 x0 = overlap_cold_start(4 * q + g, c, 16);      // (generic: see overlap_cold_start)
-    xr[q] = x0.x;
-    xi[q] = x0.y;
-  }
-  if (xs != nullptr) {
-    v4f64 wr, wi;
-    double n2 = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const double2 t = xs[(4 * q + g) * D + c];
-      wr[q] = t.x; wi[q] = t.y;
-      n2 = dfma(t.x, t.x, dfma(t.y, t.y, n2));
-    }
-    n2 = lane0(wave_sum(n2));
-    if (n2 > 1e-200 && n2 < 1e200) {
-      const double inv = 1.0 / __builtin_sqrt(n2);
-      xr = wr * inv;
-      xi = wi * inv;
-    }
-  }
+  tile16_cold_start(xr, xi);
+  if (xs != nullptr) tile16_warm_start(xs, xr, xi);
   double eta_r = 0.0, eta_i = 0.0;
   int iters = 0, status = QMPS_ST_NOT_CONVERGED;
   const v4f64 qre = {bre[0], bre[1], bre[2], bre[3]};
@@ -184,23 +96,20 @@ __device__ __forceinline__ void solve_teams_d16(const double2* sA, const double2
     double2 (*sXk)[256] = sX_all + kW16 * (k & 1);
     {
       double xar[4], xai[4];
-      to_a_layout(xr, xi, xar, xai);
+      tile16_to_a_layout(sT, xr, xi, xar, xai);
       v4f64 yr = {0, 0, 0, 0}, yi = {0, 0, 0, 0}, pr = {0, 0, 0, 0}, pi = {0, 0, 0, 0};
       cmma16_3m(xar, xai, qre, qim, yr, yi);           // Y_w = x Bm_w^+
       cmma16_3m(o.cre, o.cim, yr, yi, pr, pi);         // C_w Y_w
-#pragma unroll
-      for (int q = 0; q < 4; ++q) sXk[wave][q * 64 + lane] = make_double2(pr[q], pi[q]);
+      tile16_publish(sXk[wave], pr, pi);
     }
     team_barrier(sArrive + team, 4 * k);
     v4f64 nr = {0, 0, 0, 0}, ni = {0, 0, 0, 0};
 #pragma unroll
     for (int w = 0; w < 4; ++w) {                 // the same order in every wave of the team: bit-identical sums
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const double2 t = sXk[team * 4 + w][q * 64 + lane];
-        nr[q] += t.x;
-        ni[q] += t.y;
-      }
+      v4f64 tr, ti;
+      tile16_fetch(sXk[team * 4 + w], tr, ti);
+      nr += tr;
+      ni += ti;
     }
     iters = k;
     const bool last = k >= max_rounds;
@@ -209,30 +118,8 @@ __device__ __forceinline__ void solve_teams_d16(const double2* sA, const double2
       xi = ni;
       continue;
     }
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      a0 = dfma(xr[q], nr[q], a0);
-      a0 = dfma(xi[q], ni[q], a0);
-      a1 = dfma(xr[q], ni[q], a1);
-      a1 = dfma(-xi[q], nr[q], a1);
-      a2 = dfma(nr[q], nr[q], a2);
-      a2 = dfma(ni[q], ni[q], a2);
-      a3 = dfma(xr[q], xr[q], a3);
-      a3 = dfma(xi[q], xi[q], a3);
-    }
-    const double xx = wave_sum(a3), ixx = xx > 0.0 ? 1.0 / xx : 0.0;
-    eta_r = wave_sum(a0) * ixx;
-    eta_i = wave_sum(a1) * ixx;
-    const double nn = wave_sum(a2);
-    double rs = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const double dr = nr[q] - (eta_r * xr[q] - eta_i * xi[q]), di = ni[q] - (eta_r * xi[q] + eta_i * xr[q]);
-      rs = dfma(dr, dr, rs);
-      rs = dfma(di, di, rs);
-    }
-    const double res2 = lane0(wave_sum(rs)) * ixx;
+    double xx, nn, rs_sum;
+    const double res2 = tile16_power_test(xr, xi, nr, ni, eta_r, eta_i, xx, nn, rs_sum);
     if (res2 < tol2) {
       status = QMPS_ST_OK;
       const double inv = xx > 0.0 ? 1.0 / __builtin_sqrt(xx) : 0.0;

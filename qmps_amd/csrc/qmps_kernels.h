@@ -346,7 +346,7 @@ __device__ __forceinline__ bool power_gives_up(int k, double res2, double tol2, 
   return (l - __log2f((float)tol2)) > rate * (float)limit;
 }
 #endif
-hipError_t launch_overlap(const OverlapArgs& a, hipStream_t st);   // D = 2 (lane kernel, squaring)
+hipError_t launch_overlap(const OverlapArgs& a, hipStream_t st);   // D = 2 (lane kernel, squaring: qmps_overlap_square.hip)
 // D = 2: the whole BFGS time evolution in one launch, one wave per trajectory (qmps_evolve_d2.hip)
 constexpr int kEvolveMaxAlphas = 16;
 struct EvolveD2Args {
@@ -381,9 +381,17 @@ hipError_t launch_evolve_bfgs_d16(int kind, const EvolveD2Args& a, hipStream_t s
 // iterates and receives the fixed points; `counter` zeroed by the caller (qmps_overlap_krylov.hip)
 hipError_t launch_overlap_krylov(int D, const OverlapArgs& a, int* counter, hipStream_t st);
 hipError_t launch_overlap_krylov_pair(int D, const OverlapArgs& right, const OverlapArgs& left, hipStream_t st);   // both solves of a pair launch
-// D = 4, 8, 16: operator-form power method (qmps_overlap.hip); tensors [2][D][D]; max_rounds = cap on power steps;
-// mfma: D = 16 on the matrix cores (one wave per evaluation) instead of the generic LDS-tile kernel
+// D = 4, 8, 16: dominant eigenvalue of the map in operator form (qmps_overlap.hip dispatches); tensors [2][D][D]; max_rounds = cap on power steps /
+// squarings; mfma: D = 4, 16 on the matrix cores (qmps_overlap_square.hip, qmps_overlap_d16.hip) instead of the generic LDS-tile kernel
 hipError_t launch_overlap_d(int D, const OverlapArgs& a, bool mfma, hipStream_t st);
+// the kernel families behind it, one file each (a.B > 0)
+hipError_t launch_overlap_block(int D, const OverlapArgs& a, hipStream_t st);      // D = 4, 8, 16 (qmps_overlap_block.hip)
+hipError_t launch_overlap_square_d4(const OverlapArgs& a, hipStream_t st);
+hipError_t launch_overlap_mfma_d16(const OverlapArgs& a, hipStream_t st);
+// D = 16 on the matrix cores: four waves per evaluation (with the Krylov fall-back behind them) - or, above 2 048 evaluations without a queue, one
+inline bool overlap_d16_four_waves(const OverlapArgs& a) { return a.B <= 2048 || a.queue != nullptr; }
+// the Krylov fall-back behind a power launch (`second`: nullable, the left solve of a pair launch)
+hipError_t launch_krylov_after(int D, const OverlapArgs& a, const OverlapArgs* second, hipStream_t st);
 // psi[0] of the overlap circuit for GIVEN environments (qmps_overlap_amp.hip): a.x_in = q [B][D][D], a.eta = amplitudes [B]
 hipError_t launch_overlap_amplitude(int D, const OverlapArgs& a, hipStream_t st);
 // D = 16, at most 8192 evaluations in all: right fixed points (`right`) and left fixed points (`left`, adjoint map) in ONE launch, four waves per evaluation

@@ -1,5 +1,5 @@
 // qmps_overlap_d2.h - the D = 2 time-evolution overlap solve of ONE lane (gfx950 only), shared by overlap_lane_kernel
-// (qmps_overlap.hip) and the device-resident BFGS time evolution (qmps_evolve_d2.hip).
+// (qmps_overlap_square.hip) and the device-resident BFGS time evolution (qmps_evolve_d2.hip).
 // Reference: qmps/new_time_evolve.py:193-221, scripts/loschmidt.py:209-239, qmps/time_evolve_tools.py:20-23.
 //   T(x) = sum_{s=0..3} C_s x Bm_s^+ ,  C = WW . merge(A, A) ,  Bm = merge(B, B)
 // eta = dominant eigenvalue of T by power iteration applied 2^m steps at a time: the 4 x 4 complex matrix of T is squared

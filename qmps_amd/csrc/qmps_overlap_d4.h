@@ -1,5 +1,5 @@
 // qmps_overlap_d4.h - the D = 4 time-evolution overlap solve of ONE wave on the matrix cores (gfx950 only), shared by
-// overlap_square_d4_kernel (qmps_overlap.hip) and the device-resident BFGS time evolution (qmps_evolve_d4.hip).
+// overlap_square_d4_kernel (qmps_overlap_square.hip) and the device-resident BFGS time evolution (qmps_evolve_d4.hip).
 // Reference: qmps/new_time_evolve.py:193-221, scripts/loschmidt.py:209-239, qmps/time_evolve_tools.py:20-23.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,6 +7,7 @@
 #include "qmps_kernels.h"
 #include "qmps_device.h"
 #include "qmps_complex.h"
+#include "qmps_tile16.h"
 
 namespace qmps {
 
@@ -18,23 +19,10 @@ namespace {
 // (Gelfand), QMPS_ST_TIED.  One wave; Ap / Bp: reference / candidate tensors [2][4][4]
 // (any address space); sT: the wave's LDS scratch [kSquareD4Scratch]; (mr, mi): the final M in the accumulator layout (its largest column
 // / row are the right / left fixed points).  All results wave-uniform.  sT: kSquareD4Scratch entries per wave.
-constexpr int kSquareD4Keep = 16 * 17, kSquareD4Scratch = kSquareD4Keep + 128;
+constexpr int kSquareD4Keep = 16 * kTile16Ld, kSquareD4Scratch = kSquareD4Keep + 128;
 __device__ __forceinline__ void overlap_square_d4_item(const double2* Ap, const double2* Bp, const double2* W, double2* sT, int max_rounds, double tol2,
                                                        double& eta_r_out, double& eta_i_out, int& rounds_out, int& status_out, v4f64& mr_out, v4f64& mi_out) {
-  constexpr int LD = 17;
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
-  auto to_a_layout = [&](const v4f64& re, const v4f64& im, double (&are)[4], double (&aim)[4]) {
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sT[(4 * q + g) * LD + c] = make_double2(re[q], im[q]);
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const double2 t = sT[c * LD + 4 * kk + g];
-      are[kk] = t.x;
-      aim[kk] = t.y;
-    }
-  };
   double trr = 0.0, tri = 0.0;
     // ---- set-up through LDS: inputs at sT[0..63], then C_s[i][j] at sT[64 + 16 s + 4 i + j], Bm_s at sT[128 + ...]
     {
@@ -87,7 +75,7 @@ __device__ __forceinline__ void overlap_square_d4_item(const double2* Ap, const 
     bool nilpotent = false, collapsed = false;
     for (int m = 0; m <= max_rounds; ++m) {
       double ar[4], ai[4];
-      to_a_layout(mr, mi, ar, ai);
+      tile16_to_a_layout(sT, mr, mi, ar, ai);
       v4f64 qr = {0, 0, 0, 0}, qi = {0, 0, 0, 0};
       cmma16_3m(ar, ai, mr, mi, qr, qi);      // (three real products per k-slab: 12 instead of 16 v_mfma_f64_16x16x4 per squaring)                     // Q = M M
       // ||M M||_F^2 every round (the next power is normalised by it, a collapsed power shows in it); the rank-one test - the trace, the residual:

@@ -21,6 +21,7 @@
 #include "qmps_kernels.h"
 #include "qmps_device.h"
 #include "qmps_complex.h"
+#include "qmps_tile16.h"
 
 namespace qmps {
 
@@ -130,32 +131,20 @@ __global__ __launch_bounds__((D * D < 64) ? 64 : D * D) void overlap_g_kernel(Ov
 
 // D = 16: the same on the matrix cores, FOUR WAVES per trajectory (round 4): wave w = (t1, t2) forms A_t1 A_t2 (published through
 // LDS), then C_w = sum_t WW[w][t] A A_t, Z_w = C_w r and G_w = y^+ Z_w - three complex 16 x 16 x 16 products per wave, operands
-// loaded from HBM in the MFMA layouts (the set-up of overlap_mfma_d16x4_body, qmps_overlap.hip, does the first half the same way).
+// loaded from HBM in the MFMA layouts (the first half is that of tile16_split_setup, qmps_tile16.h, from the same pieces).
 // The generic kernel above (a thread per matrix element, three LDS stages) took 9.5 us for 256 trajectories on the critical path of a
 // gradient batch (solves -> G -> probes).
 __global__ __launch_bounds__(256) void overlap_g_d16_kernel(OverlapGradArgs p) {
-  constexpr int D = 16, N = 256, LD = 17;
-  __shared__ double2 sX[4][N];            // exchange: one accumulator-layout matrix per wave, element (q, lane) at [q * 64 + lane]
-  __shared__ double2 sT[4][D * LD];       // wave-private transposes
+  constexpr int D = 16, N = 256;
+  __shared__ double2 sX[4][N];            // exchange: one tile (tile16_publish) per wave
+  __shared__ double2 sT[4][D * kTile16Ld];       // wave-private transposes
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int64_t t = blockIdx.x;
   if (p.active != nullptr && p.active[t] == 0) return;      // skipped trajectory (uniform over the workgroup)
   const double2* Ap = (const double2*)p.A + t * (2 * N);
-  const int t1 = wave >> 1, t2 = wave & 1;
   v4f64 zr = {0, 0, 0, 0}, zi = {0, 0, 0, 0};
-  {
-    double pa[4], pai[4];
-    v4f64 qa, qai;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const double2 va = Ap[(t1 * D + c) * D + 4 * kk + g], wa = Ap[(t2 * D + 4 * kk + g) * D + c];
-      pa[kk] = va.x; pai[kk] = va.y;
-      qa[kk] = wa.x; qai[kk] = wa.y;
-    }
-    cmma16(pa, pai, qa, qai, zr, zi);       // A_t1 A_t2
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) sX[wave][q * 64 + lane] = make_double2(zr[q], zi[q]);
+  tile16_merge_pair(Ap, D, wave >> 1, wave & 1, zr, zi);       // A_t1 A_t2
+  tile16_publish(sX[wave], zr, zi);
   // r in B-layout, y^+ in A-layout ((y^+)[c][4 kk + g] = conj(y[4 kk + g][c])): the same addresses
   v4f64 rr, ri;
   double yr_[4], yin[4];
@@ -170,30 +159,9 @@ __global__ __launch_bounds__(256) void overlap_g_d16_kernel(OverlapGradArgs p) {
   }
   __syncthreads();
   v4f64 sr = {0, 0, 0, 0}, si = {0, 0, 0, 0};
-  {
-    const double2* W = (const double2*)p.WW;
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      const double2 w = W[wave * 4 + tt];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const double2 v = sX[tt][q * 64 + lane];
-        sr[q] += w.x * v.x - w.y * v.y;
-        si[q] += w.x * v.y + w.y * v.x;
-      }
-    }
-  }
-  // C_w into the A-layout (padded transpose through the wave's own LDS tile)
-  double cre[4], cim[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) sT[wave][(4 * q + g) * LD + c] = make_double2(sr[q], si[q]);
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const double2 v = sT[wave][c * LD + 4 * kk + g];
-    cre[kk] = v.x;
-    cim[kk] = v.y;
-  }
+  tile16_mix_pairs((const double2*)p.WW, wave, sX, sr, si);
+  double cre[4], cim[4];      // C_w into the A-layout
+  tile16_to_a_layout(sT[wave], sr, si, cre, cim);
   v4f64 ur = {0, 0, 0, 0}, ui = {0, 0, 0, 0}, gr = {0, 0, 0, 0}, gi = {0, 0, 0, 0};
   cmma16_3m(cre, cim, rr, ri, ur, ui);          // Z_w = C_w r
   cmma16_3m(yr_, yin, ur, ui, gr, gi);          // G_w = y^+ Z_w

@@ -3,7 +3,7 @@
 // Reference: the reference obtains eta, r (and the left vector) of the mixed transfer map from xmps `Map(...).right_fixed_point()` /
 // `.left_fixed_point()` (qmps/new_time_evolve.py:201-203, qmps/time_evolve_tools.py:84-91, scripts/loschmidt.py:212-215) and the
 // environment from `TransferMatrix(A).eigs()` (qmps/tools.py:176-182): scipy.sparse.linalg.eigs = ARPACK, implicitly restarted
-// Arnoldi, k = 1, which = 'LM'.  The power method of qmps_overlap.hip needs ~1/(1 - |eta_2/eta_1|) map applications - 10^4..10^5
+// Arnoldi, k = 1, which = 'LM'.  The power method of qmps_overlap_block.hip / qmps_overlap_d16.hip needs ~1/(1 - |eta_2/eta_1|) map applications - 10^4..10^5
 // on candidates far from the reference state (crowded rings of nearly equal-modulus eigenvalues); ARPACK does not care.  This
 // file is the library's Arnoldi: the power kernels hand a candidate over as soon as their residual history predicts a long
 // tail (status 1, steps used < max_rounds, iterate in r_out) and the kernel below finishes it.
@@ -31,6 +31,7 @@
 #include "qmps_kernels.h"
 #include "qmps_device.h"
 #include "qmps_complex.h"
+#include "qmps_tile16.h"
 
 namespace qmps {
 
@@ -65,21 +66,9 @@ enum { S_THETA = 0 /* 16 doubles */, S_G01 = 16 /* 2 */, S_RHO2 = 18 /* 1: bound
 // sG [16][16] row-major; out: sQ[r][i] (r < 16, i < KK), theta_i = y_i^H G y_i, g01 = y_0^H G y_1.  scratch >= 16*17*16 + 1024 bytes.
 __device__ __forceinline__ void rayleigh_ritz_wave(const double2* sG, double2* sQ, double* sS, char* scratch) {
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
-  double2* sT = (double2*)scratch;                 // [16][17] transposes
-  double2* sY = (double2*)(scratch + 16 * 17 * 16);       // [16] current vector
-  double* sCol = (double*)(scratch + 16 * 17 * 16 + 256);  // [16] column norms
-  auto to_a_layout = [&](const v4f64& re, const v4f64& im, double (&are)[4], double (&aim)[4]) {
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sT[(4 * q + g) * 17 + c] = make_double2(re[q], im[q]);
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const double2 t = sT[c * 17 + 4 * kk + g];
-      are[kk] = t.x;
-      aim[kk] = t.y;
-    }
-  };
+  double2* sT = (double2*)scratch;                 // [16][kTile16Ld] transposes
+  double2* sY = (double2*)(scratch + 16 * kTile16Ld * 16);       // [16] current vector
+  double* sCol = (double*)(scratch + 16 * kTile16Ld * 16 + 256);  // [16] column norms
   // deflated G in C-layout registers: element [row 4 q + g][col c]
   v4f64 gr, gi;
 #pragma unroll
@@ -103,7 +92,7 @@ __device__ __forceinline__ void rayleigh_ritz_wave(const double2* sG, double2* s
       v4f64 mr = gr * inv0, mi = gi * inv0;
       for (int m = 0; m < KSQ_ROUNDS; ++m) {
         double ar[4], ai[4];
-        to_a_layout(mr, mi, ar, ai);
+        tile16_to_a_layout(sT, mr, mi, ar, ai);
         v4f64 qr = {0, 0, 0, 0}, qi = {0, 0, 0, 0};
         cmma16_3m(ar, ai, mr, mi, qr, qi);
         double d0 = 0.0, d1 = 0.0;
@@ -318,23 +307,9 @@ __device__ __forceinline__ void overlap_krylov_body(const OverlapArgs& p, int* c
       double2* xio = (double2*)((char*)p.r_out + slot_off) + b * N;
 
       // ================= set-up of the map =================
-      // D = 16: wave w keeps C_w (A-layout) and Bm_w^+ (B-layout) in registers, as overlap_mfma_d16x4_body
+      // D = 16: wave w keeps C_w (A-layout) and Bm_w^+ (B-layout) in registers (tile16_split_setup)
       double cre[4] = {0, 0, 0, 0}, cim[4] = {0, 0, 0, 0}, bre[4] = {0, 0, 0, 0}, bimn[4] = {0, 0, 0, 0};
       if constexpr (D == 16) {
-        double2* sT = (double2*)(smem + L::oW) + wave * (16 * 17);        // (the image vectors are not in use yet)
-        auto to_a_layout = [&](const v4f64& re, const v4f64& im, double (&are)[4], double (&aim)[4]) {
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int q = 0; q < 4; ++q) sT[(4 * q + g) * 17 + c] = make_double2(re[q], im[q]);
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) {
-            const double2 t = sT[c * 17 + 4 * kk + g];
-            are[kk] = t.x;
-            aim[kk] = t.y;
-          }
-        };
-        const int t1 = wave >> 1, t2 = wave & 1;
         if (env) {
           // the environment map r -> sum_{s<2} B_s r B_s^+ : waves 0, 1 hold C_w = B_w (A-layout) and B_w^+ (B-layout = conj of the A-layout), waves 2, 3 nothing
           if (wave < 2) {
@@ -345,53 +320,11 @@ __device__ __forceinline__ void overlap_krylov_body(const OverlapArgs& p, int* c
               bre[kk] = v.x; bimn[kk] = -v.y;
             }
           }
+          __syncthreads();
         } else {
-        double pa[4], pai[4], pb[4], pbi[4];
-        v4f64 qa, qai, qb, qbi;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-          const double2 va = Ap[(t1 * D + c) * D + 4 * kk + g], vb = Bp[(t1 * D + c) * D + 4 * kk + g];
-          pa[kk] = va.x; pai[kk] = va.y;
-          pb[kk] = vb.x; pbi[kk] = vb.y;
-          const double2 wa = Ap[(t2 * D + 4 * kk + g) * D + c], wb = Bp[(t2 * D + 4 * kk + g) * D + c];
-          qa[kk] = wa.x; qai[kk] = wa.y;
-          qb[kk] = wb.x; qbi[kk] = wb.y;
+          // (transposes through the image vectors, not in use yet; the exchange region as four tiles)
+          tile16_split_setup(Ap, Bp, D, W, wave, ADJ, (double2*)(smem + L::oW) + wave * (16 * kTile16Ld), (double2 (*)[256])sP, cre, cim, bre, bimn);
         }
-        v4f64 zr = {0, 0, 0, 0}, zi = {0, 0, 0, 0};
-        cmma16(pa, pai, qa, qai, zr, zi);                       // AA_w = A_t1 A_t2
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sP[wave * N + q * 64 + lane] = make_double2(zr[q], zi[q]);
-        v4f64 yr = {0, 0, 0, 0}, yi = {0, 0, 0, 0};
-        cmma16(pb, pbi, qb, qbi, yr, yi);                       // Bm_w = B_t1 B_t2
-        if constexpr (ADJ) {
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) { bre[kk] = yr[kk]; bimn[kk] = yi[kk]; }
-        } else {
-          double tr[4], ti[4];
-          to_a_layout(yr, yi, tr, ti);
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) { bre[kk] = tr[kk]; bimn[kk] = -ti[kk]; }
-        }
-        __syncthreads();
-        v4f64 sr = {0, 0, 0, 0}, si = {0, 0, 0, 0};
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const double2 w = W[wave * 4 + t];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const double2 a = sP[t * N + q * 64 + lane];
-            sr[q] += w.x * a.x - w.y * a.y;
-            si[q] += w.x * a.y + w.y * a.x;
-          }
-        }
-        if constexpr (ADJ) {
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) { cre[kk] = sr[kk]; cim[kk] = -si[kk]; }
-        } else {
-          to_a_layout(sr, si, cre, cim);
-        }
-        }
-        __syncthreads();
       } else {
         // D = 8: tiles of C_s and Bm_s in LDS; wave s forms AA_s and Bm_s (thread (i, j) of the wave), then C_s = sum_t WW[s][t] AA_t
         double2 (*sC)[8][9] = (double2 (*)[8][9])(smem + L::oT);
@@ -436,13 +369,12 @@ __device__ __forceinline__ void overlap_krylov_body(const OverlapArgs& p, int* c
           const v4f64 qim = {bimn[0], bimn[1], bimn[2], bimn[3]};
           cmma16_3m(xar, xai, qre, qim, yr, yi);
           cmma16_3m(cre, cim, yr, yi, pr, pi);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) sP[wave * N + q * 64 + lane] = make_double2(pr[q], pi[q]);
+          tile16_publish(sP + wave * N, pr, pi);
           __syncthreads();
           double2 s = make_double2(0.0, 0.0);
 #pragma unroll
           for (int w = 0; w < 4; ++w) {
-            const double2 t = sP[w * N + wave * 64 + lane];           // register q = wave of lane (g, c): element [4 wave + g][c]
+            const double2 t = sP[w * N + tile16_at(wave, lane)];      // register q = wave of lane (g, c): element [4 wave + g][c]
             s.x += t.x;
             s.y += t.y;
           }

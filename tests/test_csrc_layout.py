@@ -7,7 +7,10 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'qmps_amd', 'csrc')
 
-SHARED_HELPERS = ('cmul', 'cmulc', 'cfma', 'cfms', 'cfma_conj', 'cfma_cj', 'cmma16', 'cmma16_3m', 'swz32', 'rx_lanes', 'crecip')
+SHARED_HELPERS = ('cmul', 'cmulc', 'cfma', 'cfms', 'cfma_conj', 'cfma_cj', 'cmma16', 'cmma16_3m', 'swz32', 'rx_lanes', 'crecip',
+                  # the wave-level steps of the 16 x 16 matrix-core solves (qmps_tile16.h)
+                  'tile16_to_a_layout', 'tile16_at', 'tile16_publish', 'tile16_fetch', 'tile16_merge_pair', 'tile16_mix_pairs',
+                  'tile16_split_setup', 'tile16_cold_start', 'tile16_warm_start', 'tile16_power_test')
 
 
 def sources():
@@ -41,3 +44,12 @@ def test_each_shared_device_helper_is_defined_once():
         assert not re.search(r'\bcmma\(', text), f
         assert not re.search(r'\bswz<', text), f
         assert not re.search(r'\brx_cross\b', text), f
+        assert 'auto to_a_layout' not in text, f
+
+
+def test_the_overlap_dispatch_file_holds_no_kernels():
+    """qmps_overlap.hip chooses the kernel family; the kernels live in one file per family."""
+    src = sources()
+    assert '__global__' not in src['qmps_overlap.hip']
+    for f in ('qmps_overlap_block.hip', 'qmps_overlap_d16.hip', 'qmps_overlap_square.hip'):
+        assert '__global__' in src[f], f

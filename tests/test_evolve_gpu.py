@@ -139,6 +139,38 @@ def test_two_sided_gradient_vs_oracle_central_differences(D, P, engine_factory):
         eng.overlap_gradient(0, X2[:3], h=h, warm=True)        # the resident fixed points belong to 5 trajectories
 
 
+@pytest.mark.parametrize('T', [5, 2049])
+def test_two_sided_gradient_with_separate_d16_solves_vs_oracle(T, engine_factory, monkeypatch):
+    """QMPS_D16_ONE_WAVE takes qmps_overlap_gradient at D = 16 off the pair launch: the right and the left fixed points come from two
+    launches of their own - up to 2 048 iterates overlap_mfma_d16x4_kernel<false, .> and <true, .> (cold: with deflation steps, warm:
+    without), beyond that overlap_mfma_d16_kernel<false> and <true>, one wave per iterate.  Objective and gradient against the
+    oracle's central differences of dense eigen-solves, on a few iterates spread over the batch."""
+    D, P, h = 16, 8, 1e-6
+    rng = np.random.default_rng(1600 + T)
+    WW = WW_of(0.05)
+    ref = rng.standard_normal((T, P))
+    X = ref + 0.03 * rng.standard_normal((T, P))
+    eng = engine_factory(D, 4096 if T * (2 * P + 1) <= 4096 else 1 << 16)
+    monkeypatch.setenv('QMPS_D16_ONE_WAVE', '1')
+    eng.overlap_set_refs_params(0, ref, WW)
+    eng.overlap_stats(reset=True)
+    f, g, st = eng.overlap_gradient(0, X, h=h, tol=1e-13)
+    assert np.all(st == 0) and eng.overlap_stats(reset=True)['evaluations'] == 2 * T
+    X2 = X + 1e-3 * rng.standard_normal(X.shape)
+    f2, g2, st2 = eng.overlap_gradient(0, X2, h=h, tol=1e-13, warm=True)
+    monkeypatch.delenv('QMPS_D16_ONE_WAVE')
+    assert np.all(st2 == 0)
+    for t in sorted({0, T // 2, T - 1}):
+        A = ER.tensor(0, D, ref[t])
+        for x, fv, gv in ((X[t], f[t], g[t]), (X2[t], f2[t], g2[t])):
+            assert abs(fv - ER.objective(0, D, A, x, WW)) < 1e-10, (t, fv)
+            for k in (0, P - 1):
+                e = np.zeros(P)
+                e[k] = h
+                g_ref = (ER.objective(0, D, A, x + e, WW) - ER.objective(0, D, A, x - e, WW)) / (2 * h)
+                assert abs(gv[k] - g_ref) < 2e-7, (t, k, gv[k], g_ref)
+
+
 # (D, ansatz kind, parameters, trajectories, steps, sweeps, shifts per parameter, seed)
 ROTO_CASES = [(2, 2, 15, 3, 3, 2, 3, 11),      # the reference's own case: ShallowFullStateTensor(2, .), new_time_evolve.py:186-187
               (2, 0, 8, 3, 3, 2, 6, 12),       # scripts/loschmidt.py:203-207: ShallowCNOTStateTensor(2, .) with 8 angles, double frequency

@@ -8,11 +8,11 @@ here each such mistake moves the compared number by 1e-6 at least (eta: 1e-5 .. 
 One test per site:
   overlap_lane_kernel (qmps_overlap_d2.h)                 test_plain_solves[2-*], test_one_reference_per_candidate[2]
   overlap_square_d4_kernel (qmps_overlap_d4.h)            test_plain_solves[4-*], test_one_reference_per_candidate[4]
-  overlap_block_kernel<4> (qmps_overlap.hip)              test_d4_power_method_in_a_child_process
-  overlap_block_kernel<8> (qmps_overlap.hip)              test_plain_solves[8-*], test_one_reference_per_candidate[8]
-  overlap_mfma_d16x4_kernel (four waves; qmps_overlap.hip) test_plain_solves[16-*], test_one_reference_per_candidate[16]
-  overlap_mfma_d16_kernel (one wave; qmps_overlap.hip)    test_d16_one_wave_kernel
-  overlap_block_kernel<16> (qmps_overlap.hip)             test_d16_tile_kernel_in_a_child_process
+  overlap_block_kernel<4> (qmps_overlap_block.hip)        test_d4_power_method_in_a_child_process
+  overlap_block_kernel<8> (qmps_overlap_block.hip)        test_plain_solves[8-*], test_one_reference_per_candidate[8]
+  overlap_mfma_d16x4_kernel (four waves; qmps_overlap_d16.hip) test_plain_solves[16-*], test_one_reference_per_candidate[16]
+  overlap_mfma_d16_kernel (one wave; qmps_overlap_d16.hip) test_d16_one_wave_kernel
+  overlap_block_kernel<16> (qmps_overlap_block.hip)       test_d16_tile_kernel_in_a_child_process
   qmps_overlap_krylov.hip, D = 8 and D = 16               test_krylov_fallback
   overlap_g_kernel, overlap_g_d16_kernel, pair kernel     test_gradient_path (qmps_overlap_grad.hip; adjoint solves, probes)
   qmps_evolve_d2.hip (build_reference, lane solves)       test_device_resident_bfgs[2] (also QMPS_EVOLVE_D2_SQUARING)
