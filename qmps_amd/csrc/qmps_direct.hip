@@ -5,9 +5,12 @@
 //   -> the real 16 x 16 transfer matrix R, four rows per lane
 //   -> (R - 1 + e_15 t^T) u = e_15 by Gauss-Jordan elimination in registers, pivot rows handed round the quad by
 //      v_mov_b32_dpp quad_perm (VALU only; no LDS, no cross-quad traffic)
-//   -> one power step as acceptance test (||T(r) - r||_F < tol; else the power method 2^m steps at a time)
+//   -> one power step as acceptance test (||T(r) - r||_F < tol; else the power method 2^m steps at a time); the cold start keeps its two
+//      halves W_00, W_11 (W_{t2 s2} = A_t2 r A_s2^+, T(r) = W_00 + W_11) and forms W_01 / W_10 where rho needs them
 //   -> LDL^H positive-definiteness test, two-site density matrix - of its upper triangle the real and imaginary parts that some
-//      term of h reads (LaneArgs::rho_need; all of it when rho is returned) - energies of all Hamiltonian terms, h from scalar loads
+//      term of h reads (LaneArgs::rho_need; all of it when rho is returned): cold start rho = tr(N W) with N_{s1 t1} = A_s1^+ A_t1 from the
+//      tensor (density_sites), warm start from B_tau = A_t1 A_t2 and the LDL^H factors (density) - energies of all Hamiltonian terms, h from
+//      scalar loads
 //   -> E (8 B per term), iterations + status (8 B), optionally r (256 B); per-wave partial sums of E.
 // One read of A and one store of E per evaluation: the environment never travels through HBM.
 // The mathematics lives in qmps_direct_core.h (shared with the CPU lock-step emulation the test-suite uses).
@@ -83,6 +86,12 @@ struct QuadOps {
   }
   __device__ __forceinline__ void uni(int s, int i, int j, V& re, V& im) const {
     const double2 v = row[(4 * s + i) * 4 + j];
+    re = v.x;
+    im = v.y;
+  }
+  // (16 B stride inside the quad, 528 B between quads: the bank pattern of `own`)
+  __device__ __forceinline__ void col(int s, int i, V& re, V& im) const {
+    const double2 v = row[(4 * s + i) * 4 + q];
     re = v.x;
     im = v.y;
   }
@@ -301,6 +310,9 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
   double x[4], us[16];
   double steps = 1.0;
   int status = QMPS_ST_OK;
+  // cold start: the site factors W_{t2 s2} = A_t2 r A_s2^+ of the acceptance step, which the density phase contracts (WARM keeps the route from
+  // the tensor: there the accepted r is not the one the last power step saw, and forming W for it would be a pass more)
+  [[maybe_unused]] Core::SiteW W;
   bool have = false;            // WARM: the evaluation's resident environment passed the acceptance test as it is
   if constexpr (WARM) {
     // Warm start (environments carried over between evaluations of unchanged / barely changed tensors): one
@@ -330,7 +342,9 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
     __builtin_amdgcn_sched_barrier(0);
     Core::normalise(o, xs);
     Core::gather(xs, us);
-    const double d2 = Core::power_step(o, xs, us, y);
+    double d2;
+    if constexpr (WARM) d2 = Core::power_step(o, xs, us, y);
+    else d2 = Core::power_step_sites(o, xs, us, p.rho_need, y, W);
     __builtin_amdgcn_sched_barrier(0);
     const bool accepted = d2 < tol2 && pivmax < Core::kMaxInversePivot;     // NaN (a zero pivot) fails both
     if (!have) {
@@ -362,8 +376,14 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
         status = left ? QMPS_ST_NOT_CONVERGED : QMPS_ST_OK;
         if (WARM) steps += 1.0;
       }
+      if constexpr (!WARM) {
+        // x changed after the acceptance step: the W of the final r, taken by the evaluations that fell back alone - the others keep the bits
+        // of their own step, so no result depends on the wave-mates
+        Core::gather(x, us);
+        Core::update_sites(o, us, p.rho_need, todo, W);
+      }
     }
-    if (WARM || __any(todo)) Core::gather(x, us);
+    if constexpr (WARM) Core::gather(x, us);
   } else {
     Core::gather(x, us);
   }
@@ -372,7 +392,9 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
   // ---- positive definiteness, two-site density matrix, energies ----
   double pre[4][4], pim[4][4];
   // (p.rho_need: the parts of rho some term of h reads; everything when rho itself is asked for)
-  const bool pd = Core::density(o, us, p.rho_need, pre, pim);
+  bool pd;
+  if constexpr (WARM) pd = Core::density(o, us, p.rho_need, pre, pim);
+  else pd = Core::density_sites(o, us, p.rho_need, W, pre, pim);
   if (status == QMPS_ST_OK && !pd) status = QMPS_ST_NOT_PD;
   if (p.acc_zero != nullptr && blockIdx.x == 0) acc_clear(p.acc_zero, p.n_terms, lane, 64);   // accumulator of a later step
   for (int t = 0; t < p.n_terms; ++t) {

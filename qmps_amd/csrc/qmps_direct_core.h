@@ -28,6 +28,7 @@
 //           O::p_and(p, q), O::p_not(p), O::any(p) -> bool
 //   tensor  o.own(s, j, re, im)   A_s[q][j]  (the lane's own row)
 //           o.uni(s, i, j, re, im) A_s[i][j]  (the same value in every lane of the quad)
+//           o.col(s, i, re, im)   A_s[i][q]  (the lane's own column; only power_step_sites / density_sites ask for it)
 #pragma once
 
 #include <stdint.h>
@@ -52,6 +53,29 @@ inline uint32_t rho_need_mask(const double* h, int n_terms) {
         if (lo != hi && !(im == 0.0)) need |= 1u << (16 + 4 * lo + hi);
       }
   return need;
+}
+
+// The site factors of rho (DirectD4::density_sites): with tau = 2 t1 + t2 and sigma = 2 s1 + s2,
+//   rho[tau][sigma] = tr(N_{s1 t1} W_{t2 s2}),   N_{s1 t1} = A_s1^+ A_t1,   W_{t2 s2} = A_t2 r A_s2^+.
+// The upper triangle (tau <= sigma, so t1 <= s1) reads N_00, N_10, N_11 and all four W; W_00 and W_11 are the two halves of the
+// acceptance step and always there.  rho_site_factors: which of the other five the mask asks for - plain integer code, the same for every
+// lane (scalar registers on the device).  rho_site_parts(f): the bits of `need` that read factor f.
+constexpr uint32_t kSiteN00 = 1u, kSiteN10 = 2u, kSiteN11 = 4u, kSiteW01 = 8u, kSiteW10 = 16u;
+constexpr uint32_t rho_site_parts(uint32_t factor) {
+  uint32_t parts = 0;
+  for (int tau = 0; tau < 4; ++tau)
+    for (int sg = tau; sg < 4; ++sg) {
+      const int t1 = tau >> 1, t2 = tau & 1, s1 = sg >> 1, s2 = sg & 1;
+      const uint32_t n = s1 == 0 ? kSiteN00 : (t1 == 0 ? kSiteN10 : kSiteN11);
+      const uint32_t w = t2 == s2 ? 0u : (t2 == 0 ? kSiteW01 : kSiteW10);
+      if (factor == n || factor == w) parts |= (1u << (4 * tau + sg)) | (sg != tau ? 1u << (16 + 4 * tau + sg) : 0u);
+    }
+  return parts;
+}
+constexpr uint32_t rho_site_factors(uint32_t need) {
+  return ((need & rho_site_parts(kSiteN00)) != 0u ? kSiteN00 : 0u) | ((need & rho_site_parts(kSiteN10)) != 0u ? kSiteN10 : 0u) |
+         ((need & rho_site_parts(kSiteN11)) != 0u ? kSiteN11 : 0u) | ((need & rho_site_parts(kSiteW01)) != 0u ? kSiteW01 : 0u) |
+         ((need & rho_site_parts(kSiteW10)) != 0u ? kSiteW10 : 0u);
 }
 
 #if defined(__HIPCC__)
@@ -232,7 +256,31 @@ struct DirectD4 {
   // us: the gathered coordinates of x.  Lane q forms row q of sum_s A_s r A_s^+ (X_s = A_s[q][:] r, then
   // X_s A_s^+) and keeps the real or imaginary part its coordinates call for.
   static QMPS_CORE_FN V power_step(const O& o, const V (&x)[4], const V (&us)[16], V (&y)[4]) {
-    V ar[2][4], ai[2][4], xr[2][4], xi[2][4];
+    V xr[2][4], xi[2][4];
+    own_rows_times_r(o, us, xr, xi);
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+      // r'[q][l] = sum_s sum_k X_s[k] conj(A_s[l][k])
+      V cr = O::splat(0.0), ci = O::splat(0.0);
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          V br, bi;
+          o.uni(s, l, k, br, bi);
+          cr = O::fma(xr[s][k], br, cr);
+          cr = O::fma(xi[s][k], bi, cr);
+          ci = O::fma(xi[s][k], br, ci);
+          ci = O::fma(-xr[s][k], bi, ci);
+        }
+      y[l] = l == 3 ? cr : O::sel(o.q_gt(l), -ci, cr);     // u[(q,l)] = Re r'[q][l] (q <= l),  Im r'[l][q] = -Im r'[q][l] (q > l)
+    }
+    normalise(o, y);
+    return dist2(o, x, y);
+  }
+  // X_s = A_s[q][:] r, s = 0, 1
+  static QMPS_CORE_FN void own_rows_times_r(const O& o, const V (&us)[16], V (&xr)[2][4], V (&xi)[2][4]) {
+    V ar[2][4], ai[2][4];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -256,25 +304,71 @@ struct DirectD4 {
         xr[s][l] = cr;
         xi[s][l] = ci;
       }
+  }
+
+  // ---- 3b. the same step with its two halves kept apart: row q of W_{t2 s2} = A_t2 r A_s2^+ = X_t2 A_s2^+, [t2][s2][l] ----
+  // T(r) = W_00 + W_11; density_sites contracts the W with the tensor-only factors N (rho_site_factors), so the density matrix starts
+  // from what the acceptance step has formed instead of from the tensor again.
+  struct SiteW {
+    V re[2][2][4], im[2][2][4];
+  };
+  // y = (W_00 + W_11)/tr and the distance to x, as power_step (another summation order: the halves are summed apart).  w: W_00 and W_11, and
+  // whichever of W_01, W_10 the mask reads (rho_site_factors(need); wave-uniform tests) - the other one is NOT written.
+  static QMPS_CORE_FN V power_step_sites(const O& o, const V (&x)[4], const V (&us)[16], uint32_t need, V (&y)[4], SiteW& w) {
+    V xr[2][4], xi[2][4];
+    own_rows_times_r(o, us, xr, xi);
+    site_w(o, xr[0], xi[0], 0, w.re[0][0], w.im[0][0]);
+    site_w(o, xr[1], xi[1], 1, w.re[1][1], w.im[1][1]);
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
-      // r'[q][l] = sum_s sum_k X_s[k] conj(A_s[l][k])
-      V cr = O::splat(0.0), ci = O::splat(0.0);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          V br, bi;
-          o.uni(s, l, k, br, bi);
-          cr = O::fma(xr[s][k], br, cr);
-          cr = O::fma(xi[s][k], bi, cr);
-          ci = O::fma(xi[s][k], br, ci);
-          ci = O::fma(-xr[s][k], bi, ci);
-        }
-      y[l] = l == 3 ? cr : O::sel(o.q_gt(l), -ci, cr);     // u[(q,l)] = Re r'[q][l] (q <= l),  Im r'[l][q] = -Im r'[q][l] (q > l)
+      const V cr = w.re[0][0][l] + w.re[1][1][l];
+      y[l] = l == 3 ? cr : O::sel(o.q_gt(l), -(w.im[0][0][l] + w.im[1][1][l]), cr);
     }
+    const uint32_t f = rho_site_factors(need);
+    if (f & kSiteW01) site_w(o, xr[0], xi[0], 1, w.re[0][1], w.im[0][1]);
+    if (f & kSiteW10) site_w(o, xr[1], xi[1], 0, w.re[1][0], w.im[1][0]);
     normalise(o, y);
     return dist2(o, x, y);
+  }
+  // (X A_s2^+)[l] = sum_k X[k] conj(A_s2[l][k])
+  static QMPS_CORE_FN void site_w(const O& o, const V (&xr)[4], const V (&xi)[4], int s2, V (&wre)[4], V (&wim)[4]) {
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+      V br, bi;
+      o.uni(s2, l, 0, br, bi);
+      V cr = O::fma(xi[0], bi, xr[0] * br), ci = O::fma(-xr[0], bi, xi[0] * br);
+#pragma unroll
+      for (int k = 1; k < 4; ++k) {
+        o.uni(s2, l, k, br, bi);
+        cr = O::fma(xr[k], br, cr);
+        cr = O::fma(xi[k], bi, cr);
+        ci = O::fma(xi[k], br, ci);
+        ci = O::fma(-xr[k], bi, ci);
+      }
+      wre[l] = cr;
+      wim[l] = ci;
+    }
+  }
+  // The W of another r (us) for the evaluations p; the others keep theirs, bit for bit - an evaluation whose environment changed after the
+  // acceptance step (the power fall-back) takes the W of its final r.  The factors the mask reads, one at a time, each by the operations of
+  // power_step_sites.
+  static QMPS_CORE_FN void update_sites(const O& o, const V (&us)[16], uint32_t need, P p, SiteW& w) {
+    V xr[2][4], xi[2][4];
+    own_rows_times_r(o, us, xr, xi);
+    const uint32_t f = rho_site_factors(need);
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        if (t2 != s2 && !(f & (t2 == 0 ? kSiteW01 : kSiteW10))) continue;
+        V tre[4], tim[4];
+        site_w(o, xr[t2], xi[t2], s2, tre, tim);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+          w.re[t2][s2][l] = O::sel(p, tre[l], w.re[t2][s2][l]);
+          w.im[t2][s2][l] = O::sel(p, tim[l], w.im[t2][s2][l]);
+        }
+      }
   }
 
   // ---- 4. fall-back: the power method 2^m steps at a time from r_0 = 1/4, Rc <- Rc Rc in the quad layout ----
@@ -412,6 +506,43 @@ struct DirectD4 {
     return e;
   }
 
+  // r = L D L^H, replicated in the four lanes: rre / rim = r[k][l] (k <= l) out of the coordinates us, L strictly below the diagonal,
+  // d the pivots as they come out; a pivot <= 0 divides as 1.  Returns "every pivot > 0".
+  static QMPS_CORE_FN P ldl(const V (&us)[16], V (&rre)[4][4], V (&rim)[4][4], V (&lre)[4][4], V (&lim)[4][4], V (&d)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int l = k; l < 4; ++l) {
+        rre[k][l] = us[4 * k + l];
+        rim[k][l] = k == l ? O::splat(0.0) : us[4 * l + k];
+      }
+    P pd = O::gt0(rre[0][0]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      V dj = rre[j][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) dj = O::fma(-(lre[j][k] * lre[j][k] + lim[j][k] * lim[j][k]), d[k], dj);
+      d[j] = dj;
+      pd = O::p_and(pd, O::gt0(dj));
+      const V inv = O::rcp(O::sel(O::gt0(dj), dj, O::splat(1.0)));
+#pragma unroll
+      for (int i = j + 1; i < 4; ++i) {
+        V cr = rre[j][i], ci = -rim[j][i];   // r[i][j] = conj(r[j][i])
+#pragma unroll
+        for (int k = 0; k < j; ++k) {
+          // L[i][k] conj(L[j][k]) d_k
+          const V pr = lre[i][k] * lre[j][k] + lim[i][k] * lim[j][k];
+          const V pi = lim[i][k] * lre[j][k] - lre[i][k] * lim[j][k];
+          cr = O::fma(-pr, d[k], cr);
+          ci = O::fma(-pi, d[k], ci);
+        }
+        lre[i][j] = cr * inv;
+        lim[i][j] = ci * inv;
+      }
+    }
+    return pd;
+  }
+
   // ---- 5. positive-definiteness of r (LDL^H pivots > 0: the criterion of cholesky(r), qmps/tools.py:182) and the
   //         lane's share of the two-site density matrix rho[tau][sigma] = tr(B_tau r B_sigma^+), tau <= sigma ----
   // us: all sixteen coordinates of r (trace 1).  Lane q contributes row q of B_tau = A_t1 A_t2 (tau = 2 t1 + t2).
@@ -421,43 +552,8 @@ struct DirectD4 {
   // need (rho_need_mask; the same for every lane of the wave): an entry whose bit is clear is not computed and left exactly 0.0 - in both
   // routes; the entries that are computed see the same operations in the same order whatever the mask
   static QMPS_CORE_FN P density(const O& o, const V (&us)[16], uint32_t need, V (&pre)[4][4], V (&pim)[4][4]) {
-    // r[k][l], k <= l
-    V rre[4][4], rim[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int l = k; l < 4; ++l) {
-        rre[k][l] = us[4 * k + l];
-        rim[k][l] = k == l ? O::splat(0.0) : us[4 * l + k];
-      }
-    // LDL^H (replicated in the four lanes)
-    P pd = O::gt0(rre[0][0]);
-    V lre[4][4], lim[4][4], d[4];
-    {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        V dj = rre[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) dj = O::fma(-(lre[j][k] * lre[j][k] + lim[j][k] * lim[j][k]), d[k], dj);
-        d[j] = dj;
-        pd = O::p_and(pd, O::gt0(dj));
-        const V inv = O::rcp(O::sel(O::gt0(dj), dj, O::splat(1.0)));
-#pragma unroll
-        for (int i = j + 1; i < 4; ++i) {
-          V cr = rre[j][i], ci = -rim[j][i];   // r[i][j] = conj(r[j][i])
-#pragma unroll
-          for (int k = 0; k < j; ++k) {
-            // L[i][k] conj(L[j][k]) d_k
-            const V pr = lre[i][k] * lre[j][k] + lim[i][k] * lim[j][k];
-            const V pi = lim[i][k] * lre[j][k] - lre[i][k] * lim[j][k];
-            cr = O::fma(-pr, d[k], cr);
-            ci = O::fma(-pi, d[k], ci);
-          }
-          lre[i][j] = cr * inv;
-          lim[i][j] = ci * inv;
-        }
-      }
-    }
+    V rre[4][4], rim[4][4], lre[4][4], lim[4][4], d[4];
+    const P pd = ldl(us, rre, rim, lre, lim, d);
     V bre[4][4], bim[4][4];
     b_rows(o, bre, bim);
     // r = L D L^H:  rho[tau][sigma] = sum_k d_k G_tau[k] conj(G_sigma[k]) with G_tau = (row q of B_tau) L.  L is unit lower
@@ -579,6 +675,98 @@ struct DirectD4 {
           pim[tau][sg] = ci;
         }
     }
+  }
+
+  // ---- 5c. the same test and the same rho from the site factors: by cyclicity of the trace, for ANY tensor and ANY r,
+  //   rho[tau][sigma] = tr(A_t1 A_t2 r A_s2^+ A_s1^+) = tr(N_{s1 t1} W_{t2 s2}),   N_{s1 t1} = A_s1^+ A_t1,   W_{t2 s2} = A_t2 r A_s2^+
+  // and lane q's share is sum_l W_{t2 s2}[q][l] N_{s1 t1}[l][q]: row q of W (power_step_sites has it), column q of N (64 multiply-adds
+  // from the tensor).  Where `density` pays 384 for B, G = B L and the pivot weights whatever the mask, this route pays 64 per factor
+  // the mask reads on top of the acceptance step's W_00, W_11: 256 for TFIM and XXZ, 320 for every part.  r is not factored for rho, so
+  // an r that fails the pivot test needs no route of its own.  One N is live at a time; a part the mask leaves out is exactly 0.0, and a
+  // part that is computed sees the same operations in the same order whatever the mask.
+  static QMPS_CORE_FN P density_sites(const O& o, const V (&us)[16], uint32_t need, const SiteW& w, V (&pre)[4][4], V (&pim)[4][4]) {
+    P pd;
+    {
+      V rre[4][4], rim[4][4], lre[4][4], lim[4][4], d[4];
+      pd = ldl(us, rre, rim, lre, lim, d);
+    }
+#pragma unroll
+    for (int tau = 0; tau < 4; ++tau)
+#pragma unroll
+      for (int sg = tau; sg < 4; ++sg) {
+        pre[tau][sg] = O::splat(0.0);
+        pim[tau][sg] = O::splat(0.0);
+      }
+    static_for<3>([&](auto F) {
+      constexpr int s1 = decltype(F)::value == 0 ? 0 : 1, t1 = decltype(F)::value == 2 ? 1 : 0;
+      constexpr uint32_t parts = rho_site_parts(1u << decltype(F)::value);      // kSiteN00, kSiteN10, kSiteN11
+      if (need & parts) {
+        // column q of N_{s1 t1}: N[l][q] = sum_i conj(A_s1[i][l]) A_t1[i][q]
+        V cr[4], ci[4], nre[4], nim[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o.col(t1, i, cr[i], ci[i]);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+          V ur, ui;
+          o.uni(s1, 0, l, ur, ui);
+          V re = O::fma(ui, ci[0], ur * cr[0]), im = O::fma(-ui, cr[0], ur * ci[0]);
+#pragma unroll
+          for (int i = 1; i < 4; ++i) {
+            o.uni(s1, i, l, ur, ui);
+            re = O::fma(ur, cr[i], re);
+            re = O::fma(ui, ci[i], re);
+            im = O::fma(ur, ci[i], im);
+            im = O::fma(-ui, cr[i], im);
+          }
+          nre[l] = re;
+          nim[l] = im;
+        }
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {       // (the tests of the parts follow)
+          QMPS_COMPUTED_HERE(nre[l]);
+          QMPS_COMPUTED_HERE(nim[l]);
+        }
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+          for (int s2 = 0; s2 < 2; ++s2) {
+            const int tau = 2 * t1 + t2, sg = 2 * s1 + s2;
+            if (tau > sg) continue;
+            if ((need >> (4 * tau + sg)) & 1u) {
+              V c = w.re[t2][s2][0] * nre[0];
+              c = O::fma(-w.im[t2][s2][0], nim[0], c);
+#pragma unroll
+              for (int l = 1; l < 4; ++l) {
+                c = O::fma(w.re[t2][s2][l], nre[l], c);
+                c = O::fma(-w.im[t2][s2][l], nim[l], c);
+              }
+              pre[tau][sg] = c;
+            }
+          }
+        // (the imaginary parts of the factor behind one test of their own: a real Hamiltonian passes three tests more, not nine)
+        if ((need & parts) >> 16) {
+#pragma unroll
+          for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+              const int tau = 2 * t1 + t2, sg = 2 * s1 + s2;
+              if (tau >= sg) continue;
+              if ((need >> (16 + 4 * tau + sg)) & 1u) {
+                V c = w.re[t2][s2][0] * nim[0];
+                c = O::fma(w.im[t2][s2][0], nre[0], c);
+#pragma unroll
+                for (int l = 1; l < 4; ++l) {
+                  c = O::fma(w.re[t2][s2][l], nim[l], c);
+                  c = O::fma(w.im[t2][s2][l], nre[l], c);
+                }
+                pim[tau][sg] = c;
+              }
+            }
+        }
+      }
+    });
+    QMPS_SCHED_FENCE();
+    return pd;
   }
 
   // E = Re sum_{s,t} h[s][t] rho[t][s] from the upper triangle of rho; h: 16 complex numbers (re, im interleaved),

@@ -7,8 +7,10 @@ Without --asm, qmps_amd/csrc/qmps_direct.hip is cross-compiled for gfx950 with -
 temporary directory and its device assembly is read.  The kernel body (default energy_direct_d4_kernel<-1, false>, the
 benchmark's) is cut into phases at the sched_barrier fences of qmps_direct_core.h / qmps_direct.hip and, per phase, the
 f64 VALU, DPP moves, v_cndmask, ds_read and s_nop instructions are counted, with every VALU instruction as the total.
-Counts are static (one pass over the text); the rare phases (fall-back, density of an r that is not positive definite)
-are code that the common path branches over, and "common path" is the total without them.
+Counts are static (one pass over the text); the rare phases (the fall-back with its hand-over of the site factors; in older
+sources the density of an r that is not positive definite) are code that the common path branches over, and "common path" is
+the total without them.  The compiler moves arithmetic whose result is read late (the LDL^H pivots: only the status reads them)
+down to its reader, across the fences: compare totals rather than single phases.
 --all lists the register and scratch use of every energy_direct_d4_kernel / energy_only_d4_kernel instantiation.
 """
 import argparse
@@ -23,7 +25,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'qmps_amd', 'csrc')
 DEFAULT_KERNEL = '_ZN4qmps23energy_direct_d4_kernelILin1ELb0EEEvNS_8LaneArgsE'
 # the fences of the cold-start kernel, in order (qmps_direct.hip: energy_direct_d4_kernel)
-PHASES = ['load+build', 'solve', 'accept', 'fallback', 'density', 'density not-PD', 'energy']
+PHASES = ['load+build', 'solve', 'accept', 'fallback', 'density', 'energy']
+# sources whose density went through the LDL^H factors, with a branch of its own for an r that is not positive definite
+PHASES_LDL = ['load+build', 'solve', 'accept', 'fallback', 'density', 'density not-PD', 'energy']
 # sources before the density route had its own fences: density and energy in one phase
 PHASES_OLD = ['load+build', 'solve', 'accept', 'fallback', 'density+energy']
 RARE = ['fallback', 'density not-PD']     # branches the common path skips
@@ -94,7 +98,7 @@ def main():
         lines = open(path).read().split('\n')
     text, res = body(lines, a.kernel)
     phases = mix(text)
-    names = next((n for n in (PHASES, PHASES_OLD) if len(n) == len(phases)), [f'phase {i}' for i in range(len(phases))])
+    names = next((n for n in (PHASES, PHASES_LDL, PHASES_OLD) if len(n) == len(phases)), [f'phase {i}' for i in range(len(phases))])
     print(f'{a.kernel}')
     print(f'{"phase":<16}' + ''.join(f'{c:>9}' for c in COLS))
     tot = collections.Counter()
@@ -102,7 +106,7 @@ def main():
         tot.update(p)
         print(f'{n:<16}' + ''.join(f'{p[c]:>9}' for c in COLS))
     print(f'{"total":<16}' + ''.join(f'{tot[c]:>9}' for c in COLS))
-    if names in (PHASES, PHASES_OLD):
+    if names in (PHASES, PHASES_LDL, PHASES_OLD):
         common = tot.copy()
         for n in RARE:
             if n in names:
