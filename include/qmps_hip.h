@@ -95,7 +95,8 @@ extern "C" {
 #define QMPS_ENV_DIRECT 2
 /* flag (OR into `flags` of qmps_energy_launch): do not store the environments r[B][D][D] (QMPS_ENV_DIRECT only; saves
  * 16 D^2 bytes of HBM writes per evaluation).  qmps_get_env / qmps_get_rdm / qmps_energy_only_launch then fail with
- * QMPS_ERR_STATE until a launch without the flag has run. */
+ * QMPS_ERR_STATE until a launch without the flag has run - unless the launch was a QMPS_FLAG_WARM_RESIDENT one over environments an
+ * earlier launch stored for the same states, which it reads and leaves as they are (RESIDENT RESULTS). */
 #define QMPS_FLAG_NO_ENV_OUT 0x100
 /* flag: the launch also accumulates cost[t] = sum_b E[b][t] inside the energy kernel (the fused D = 4 kernel of
  * QMPS_ENV_DIRECT, the D = 2 / D = 4 lane kernels of the iterative solvers - not the D = 4 squaring path, whose energy
@@ -195,7 +196,18 @@ int qmps_abi_version(void);
  * 6.7: qmps_ansatz_probe (the tensors of the device ansatz builders: plain, rotosolve-shifted and central-difference batches; test hook).
  *      Added later without a bump (detect them by the symbol's presence): qmps_correlators, the two-point functions of the resident states;
  *      qmps_entanglement, their Schmidt spectra and entanglement entropies; qmps_correlator_sums, the sums over all distances of their
- *      connected two-point functions (structure factors). */
+ *      connected two-point functions (structure factors).
+ *      Changed later without a bump (same signatures; nothing a caller can detect beforehand, a refusal is an error code):
+ *      RESIDENT RESULTS (below): the context knows per evaluation slot, not per context, what its buffers hold, and read-backs that used to return
+ *      whatever the buffer held now fail with QMPS_ERR_STATE (same signatures).  qmps_get_env, qmps_get_rdm, qmps_energy_only_launch, qmps_correlators,
+ *      qmps_entanglement, qmps_correlator_sums: on a window no launch has stored environments for (another window had them), and after a
+ *      QMPS_FLAG_NO_ENV_OUT launch over a qmps_set_env_guess (they returned the guess).  qmps_get_energies: for energies no energy launch wrote since the
+ *      states or the number of terms were set (also after qmps_evolve_rotosolve, whose objectives it returned), and - when iters or status are asked
+ *      for - where an overlap launch has since written them (pass NULL for both to read the energies alone).  qmps_get_status: where no launch has covered the window since the states were set.  qmps_overlap_get,
+ *      qmps_overlap_get_objective: where no overlap launch has covered the window since the candidates were set; r_out: where the last launch over the
+ *      window kept no fixed points (it returned those of an earlier launch).  QMPS_FLAG_WARM_RESIDENT and qmps_set_env_guess start a solve only on
+ *      the slots they cover; a window outside them starts cold.  qmps_get_states after qmps_evolve_bfgs / qmps_evolve_bfgs_device: they leave no resident
+ *      states (it returned a ladder batch, the states of an earlier call, or failed, depending on the path taken). */
 int qmps_abi_minor(void);
 const char* qmps_last_error(void);
 /* Test hook for the contract above ("nothing throws across the ABI"): raises a C++ exception inside the library - kind 1
@@ -315,6 +327,37 @@ int qmps_set_window(qmps_ctx* ctx, int64_t first);
 /* optional warm start r0[B][D][D] complex128 (Hermitian, any positive trace); NULL = identity/D */
 int qmps_set_env_guess(qmps_ctx* ctx, int64_t B, const double* r0);
 
+/* ---- RESIDENT RESULTS: what the read-backs return, and when they refuse ---------------------
+ * A context keeps, per evaluation slot, what its buffers hold: the environments a read-back may return (stored by an energy launch, or given by
+ * qmps_set_env_guess over [0, B)), the energies of an energy launch, the iteration counts and statuses that belong to them, and the results and
+ * fixed points of an overlap launch.  Launches and read-backs address a window (qmps_set_window); a read-back over a window some slot of which does
+ * not hold what it asks for fails with QMPS_ERR_STATE - it never returns what a launch over other states, over another window or of another family
+ * left in the buffer.
+ *   - An upload (qmps_set_states*, also inside the one-shot calls) replaces the resident states and outdates all of them: energies, counts, statuses,
+ *     environments, guesses, overlap results and fixed points, on every window.  (The fixed points stay usable as the START of a QMPS_OVERLAP_WARM
+ *     launch over moved candidates; qmps_set_env_guess after the upload gives the new states their guesses.)
+ *   - An energy launch writes energies, counts and statuses over its window, and environments unless QMPS_FLAG_NO_ENV_OUT.  With the flag the window's
+ *     environments can not be read back afterwards - a guess of qmps_set_env_guess the launch started from stays the start of the next solve, but is
+ *     not the launch's result - except those an earlier launch stored for the same states, which a QMPS_FLAG_WARM_RESIDENT launch reads and leaves
+ *     as they are.  An energy launch outdates the overlap results and fixed points of its window.  qmps_set_hamiltonian with another number
+ *     of terms outdates the energies (their layout is [evaluation][term]).
+ *   - The iteration counts and statuses belong to the energy launch that wrote the energies: qmps_energy_only_launch and qmps_get_rdm write energies
+ *     (and need environments over their window) but solve nothing and leave counts and statuses as they are; over evaluations no energy launch
+ *     has solved since the states were set they report 0 iterations and QMPS_STATUS_OK (nothing was iterated, nothing was tested).
+ *   - An overlap launch takes over the iteration counts and statuses of its window and outdates every environment and guess of the context (its
+ *     fixed points share their buffer).  Without QMPS_OVERLAP_WANT_R the window keeps the fixed points of the launch before as a start, not as a
+ *     result: qmps_overlap_get refuses r_out.
+ *   - qmps_overlap_gradient leaves its T iterates resident with their fixed points (QMPS_OVERLAP_WARM); otherwise the gradient and evolve calls outdate
+ *     environments, energies' counts and statuses and overlap results; qmps_evolve_rotosolve also the energies (their buffer holds its objectives).
+ *     qmps_evolve_rotosolve leaves its T final vectors resident as states; qmps_evolve_bfgs and qmps_evolve_bfgs_device leave no resident states
+ *     (their results are their outputs) - qmps_evolve_bfgs the fixed points of its last gradient batch, where QMPS_BFGS_WARM and a
+ *     QMPS_OVERLAP_WARM gradient of the same T look for them (D = 4, 8, 16).
+ *   - qmps_rotosolve / qmps_double_rotosolve leave their R final vectors resident as one solved batch: states, energies, counts, statuses, environments.
+ *   - The two-site unit cell (qmps_cell2_energy_batch*) is a one-shot call: results at the start of the buffers, read back by qmps_get_energies /
+ *     qmps_get_status; it leaves no single-site states and no environments.
+ *   - The observables, qmps_ansatz_probe, qmps_roto_rule_probe, qmps_su_unitaries, qmps_opt_env_objective and the brick-wall calls change nothing of this.
+ *   - qmps_get_cost returns the cost of the last qmps_cost_launch, which no other call writes. */
+
 /* ---- the hot path ---------------------------------------------------------------------- */
 /* One pass over the resident batch: power-iteration right environment + two-site energy for
  * each of the n_terms Hamiltonians.  Replaces qmps/tools.py:176-182 (get_env_exact) +
@@ -341,7 +384,7 @@ int qmps_sum_energies(qmps_ctx* ctx, int64_t B, double* cost /* [n_terms] */);
 /* ---- outputs (HBM -> host; each waits for outstanding launches) ------------------------- */
 int qmps_get_energies(qmps_ctx* ctx, int64_t B, double* E /* [B][n_terms] */, int32_t* iters /* [B] or NULL */,
                       int32_t* status /* [B] or NULL */);
-/* per-evaluation status of the last launch over the window (energy or overlap), without the energies */
+/* per-evaluation status of the last launch over the window (energy or overlap), without the energies; QMPS_ERR_STATE where none has covered it */
 int qmps_get_status(qmps_ctx* ctx, int64_t B, int32_t* status /* [B] */);
 /* r[B][D][D] complex128, Hermitian, tr r = 1 (the dominant right eigen-matrix returned by
  * xmps TransferMatrix(A).eigs() at qmps/tools.py:181, up to its normalisation) */

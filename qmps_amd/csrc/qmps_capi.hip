@@ -320,7 +320,7 @@ int qmps_set_states(qmps_ctx* c, int64_t B, const double* states, int kind) try 
   c->n_states = B;
   c->window = 0;
   c->have_guess = false;
-  c->have_env = false;
+  forget_results(c);
   c->ans_have = false;
   c->tensors_valid = true;
   return QMPS_OK;
@@ -377,7 +377,7 @@ int qmps_set_states_ansatz(qmps_ctx* c, int64_t B, int kind, int n_params, const
   if (!c->defer_sync) HIP_TRY(hipStreamSynchronize(c->stream));
   c->window = 0;
   c->have_guess = false;
-  c->have_env = false;
+  forget_results(c);
   return QMPS_OK;
 }
 QMPS_API_CATCH
@@ -399,7 +399,7 @@ int qmps_set_states_su(qmps_ctx* c, int64_t B, const double* params) try {
   c->n_states = B;
   c->window = 0;
   c->have_guess = false;
-  c->have_env = false;
+  forget_results(c);
   c->ans_have = false;
   c->tensors_valid = true;
   return QMPS_OK;
@@ -457,6 +457,7 @@ int qmps_set_hamiltonian(qmps_ctx* c, int n_terms, const double* h) try {
     for (int sl = 0; sl < qmps_ctx::kCostSlots; ++sl)
       for (int ps = 0; ps < qmps_ctx::kMaxGroup; ++ps) c->acc_dirty[sl][ps] = true;
   }
+  if (n_terms != c->n_terms) c->energies.clear();     // d_E is laid out [evaluation][term]: the resident rows no longer line up
   c->n_terms = n_terms;
   return QMPS_OK;
 }
@@ -473,7 +474,9 @@ int qmps_set_env_guess(qmps_ctx* c, int64_t B, const double* r0) try {
   HIP_TRY(hipMemcpyAsync(c->d_r, r0, (size_t)B * env_bytes(c), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->have_guess = true;
-  c->have_env = true;
+  c->env.add(0, B);
+  c->env_guessed.add(0, B);
+  c->env_start.add(0, B);
   c->have_overlap_x = false;
   c->grad_warm_T = 0;          // d_r no longer holds the right fixed points of a gradient batch
   return QMPS_OK;

@@ -18,7 +18,7 @@ qmps::LaneArgs make_args(qmps_ctx* c, int64_t B, int max_iter, double tol, bool 
   memset(&a, 0, sizeof(a));
   a.A = win_A(c);
   a.h = c->d_h;
-  a.r_in = solve ? (c->have_guess ? win_r(c) : nullptr) : win_r(c);
+  a.r_in = solve ? (c->have_guess && window_has_start(c, B) ? win_r(c) : nullptr) : win_r(c);   // (a guess covers the slots it was given for)
   a.r_out = solve ? win_r(c) : nullptr;
   a.rho_out = c->want_rho ? (char*)c->d_rho + (size_t)c->window * 256 : nullptr;
   a.rho_need = a.rho_out != nullptr ? qmps::kRhoNeedAll : c->rho_need;   // rho itself: every entry; otherwise what h reads
@@ -192,7 +192,7 @@ int energy_squaring_d4(qmps_ctx* c, qmps::LaneArgs& a, int, KernelTimer& t) {
     q.r_in = win_r(c); q.work_count = c->d_work_count; q.work_idx = c->d_work_idx;
     e.idx_list = c->d_work_idx; e.idx_count = c->d_work_count;
   } else {
-    q.r_in = c->have_guess ? win_r(c) : nullptr;
+    q.r_in = c->have_guess && window_has_start(c, B) ? win_r(c) : nullptr;
     if (int rc = cost_sink(c, e, false, pair ? (B + 31) / 32 : (B + 63) / 64, 64)) return rc;   // (pair: one partial per 32 items)
   }
   // grid-stride workgroups of 4 waves: whole generations of the resident capacity (5 workgroups per CU), at most three
@@ -243,7 +243,7 @@ int qmps_energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int fla
     return fail(QMPS_ERR_ARG, "unknown environment solver %d", solver);
   if ((flags & ~0xff) & ~(QMPS_FLAG_NO_ENV_OUT | QMPS_FLAG_ACCUMULATE_COST | QMPS_FLAG_WARM_RESIDENT | QMPS_FLAG_KRYLOV_FALLBACK)) return fail(QMPS_ERR_ARG, "unknown flag bits 0x%x", flags & ~0xff);
   const bool warm_resident = (flags & QMPS_FLAG_WARM_RESIDENT) != 0;
-  if (warm_resident && !c->have_env) return fail(QMPS_ERR_STATE, "QMPS_FLAG_WARM_RESIDENT: no resident environments (run a launch that stores them, or qmps_set_env_guess)");
+  if (warm_resident && !c->env_start.any()) return fail(QMPS_ERR_STATE, "QMPS_FLAG_WARM_RESIDENT: no resident environments (run a launch that stores them, or qmps_set_env_guess)");
   const bool direct = solver == QMPS_ENV_DIRECT && c->D == 4;
   if ((flags & QMPS_FLAG_NO_ENV_OUT) && !direct) return fail(QMPS_ERR_ARG, "QMPS_FLAG_NO_ENV_OUT needs QMPS_ENV_DIRECT at D = 4");
   const bool accumulate = (flags & QMPS_FLAG_ACCUMULATE_COST) != 0;
@@ -262,7 +262,8 @@ int qmps_energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int fla
   if (!fused)
     if (int rc = ensure_tensors(c)) return rc;
   qmps::LaneArgs a = make_args(c, B, max_iter, tol, true);
-  if (warm_resident) a.r_in = win_r(c);
+  // (a window none of whose slots was ever stored or guessed starts cold, as documented: its part of d_r holds whatever was there)
+  if (warm_resident) a.r_in = window_has_start(c, B) ? win_r(c) : nullptr;
   if (fused) {
     const double* rows = c->ans_src ? c->ans_src : c->d_params;
     a.ans_params = c->ans_nsh > 0 ? rows : rows + (size_t)c->window * c->ans_P;
@@ -272,10 +273,26 @@ int qmps_energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int fla
   KernelTimer timer(c, periodic_timing(c));
   if (int rc = run(c, a, flags, timer)) return rc;
   if (!c->capturing) c->launches++;
-  // only the direct D = 4 path may store no environments (QMPS_FLAG_NO_ENV_OUT): a warm launch that stores nothing leaves the
-  // resident guesses in place
-  if (a.r_out != nullptr) c->have_env = true;
-  else if (a.r_in == nullptr) c->have_env = false;
+  // only the direct D = 4 path may store no environments (QMPS_FLAG_NO_ENV_OUT).  A warm launch that stores nothing leaves what it started
+  // from in place: environments an earlier launch stored for these states stay what they were; guesses stay the start of the next solve,
+  // but a launch has run over them and they are not its result - they can no longer be read back as environments (include/qmps_hip.h)
+  const int64_t lo = c->window, hi = c->window + B;
+  if (a.r_out != nullptr) {
+    c->env.add(lo, hi);
+    c->env_start.add(lo, hi);
+    c->env_guessed.remove(lo, hi);
+  } else if (a.r_in == nullptr) {
+    c->env.remove(lo, hi);
+    c->env_start.remove(lo, hi);
+    c->env_guessed.remove(lo, hi);
+  } else if (c->env_guessed.touches(lo, hi)) {
+    c->env.remove(lo, hi);
+    c->env_guessed.remove(lo, hi);
+  }
+  c->energies.add(lo, hi);
+  c->counts.add(lo, hi);
+  c->overlap_vals.remove(lo, hi);     // (rounds and statuses of an overlap launch over these slots are gone)
+  c->overlap_x.remove(lo, hi);
   return QMPS_OK;
 }
 QMPS_API_CATCH
@@ -285,10 +302,20 @@ int qmps_energy_only_launch(qmps_ctx* c, int64_t B) try {
   if (int rc = check_window(c, B)) return rc;
   if (c->window + B > c->n_states) return fail(QMPS_ERR_STATE, "window [%lld, %lld) but only %lld states are resident", (long long)c->window, (long long)(c->window + B), (long long)c->n_states);
   if (c->n_terms < 1) return fail(QMPS_ERR_STATE, "qmps_set_hamiltonian has not been called");
-  if (!c->have_env) return fail(QMPS_ERR_STATE, "no resident environment: run qmps_energy_launch or qmps_set_env_guess first");
+  if (!c->env.covers(c->window, c->window + B))
+    return fail(QMPS_ERR_STATE, "no resident environment for the window [%lld, %lld): run qmps_energy_launch (storing them) or qmps_set_env_guess over it first", (long long)c->window, (long long)(c->window + B));
   if (int rc = ensure_tensors(c)) return rc;
   qmps::LaneArgs a = make_args(c, B, 1, 1.0, false);
   c->partials_B = -1;
+  c->energies.add(c->window, c->window + B);
+  if (B > 0 && !c->counts.covers(c->window, c->window + B)) {
+    // nothing solved these evaluations since their states were set: the pass iterates nothing and tests nothing, and says so, instead
+    // of leaving the counts and statuses of another launch beside its energies
+    HIP_TRY(hipMemsetAsync(win_iters(c), 0, (size_t)B * sizeof(int32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(win_status(c), 0, (size_t)B * sizeof(int32_t), c->stream));
+    c->counts.add(c->window, c->window + B);
+    c->overlap_vals.remove(c->window, c->window + B);
+  }
   if (c->D == 16 && !documented_switch("QMPS_D16_BLOCK"))
     HIP_TRY(qmps::launch_energy_mfma(c->D, a, false, c->stream));
   else if (c->D == 4 && tuning_knob("QMPS_ENERGY_PAIR") == nullptr)
@@ -319,6 +346,13 @@ int qmps_get_energies(qmps_ctx* c, int64_t B, double* E, int32_t* iters, int32_t
   if (int rc = bind(c)) return rc;
   if (int rc = check_window(c, B)) return rc;
   if (c->n_terms < 1) return fail(QMPS_ERR_STATE, "no energies resident");
+  // what the window's slots hold must belong together: energies of the resident states, and - when asked for - the iteration counts
+  // and statuses of the launch that computed them, not those an overlap launch wrote over them since
+  // (an empty window asks for nothing)
+  if (B > 0 && E && !c->energies.covers(c->window, c->window + B))
+    return fail(QMPS_ERR_STATE, "no energies resident for the window [%lld, %lld): no energy launch has covered it since the states, or the number of terms, were set", (long long)c->window, (long long)(c->window + B));
+  if (B > 0 && (iters || status) && !c->counts.covers(c->window, c->window + B))
+    return fail(QMPS_ERR_STATE, "the iteration counts and statuses of the window [%lld, %lld) are not those of an energy launch (qmps_overlap_get / qmps_get_status read an overlap launch's)", (long long)c->window, (long long)(c->window + B));
   if (E) HIP_TRY(hipMemcpyAsync(E, win_E(c), (size_t)B * c->n_terms * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (iters) HIP_TRY(hipMemcpyAsync(iters, win_iters(c), (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (status) HIP_TRY(hipMemcpyAsync(status, win_status(c), (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -331,6 +365,8 @@ int qmps_get_status(qmps_ctx* c, int64_t B, int32_t* status) try {
   if (int rc = bind(c)) return rc;
   if (int rc = check_window(c, B)) return rc;
   if (!status) return fail(QMPS_ERR_ARG, "null status");
+  if (B > 0 && !c->counts.covers(c->window, c->window + B) && !c->overlap_vals.covers(c->window, c->window + B))
+    return fail(QMPS_ERR_STATE, "no launch, energy or overlap, has covered the window [%lld, %lld) since the states were set", (long long)c->window, (long long)(c->window + B));
   HIP_TRY(hipMemcpyAsync(status, win_status(c), (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return QMPS_OK;
@@ -341,7 +377,7 @@ int qmps_get_env(qmps_ctx* c, int64_t B, double* r) try {
   if (int rc = bind(c)) return rc;
   if (int rc = check_window(c, B)) return rc;
   if (!r) return fail(QMPS_ERR_ARG, "null r");
-  if (!c->have_env) return fail(QMPS_ERR_STATE, "no resident environment");
+  if (!c->env.covers(c->window, c->window + B)) return fail(QMPS_ERR_STATE, "no resident environment for the window [%lld, %lld)", (long long)c->window, (long long)(c->window + B));
   HIP_TRY(hipMemcpyAsync(r, win_r(c), (size_t)B * env_bytes(c), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return QMPS_OK;
@@ -352,7 +388,7 @@ int qmps_get_rdm(qmps_ctx* c, int64_t B, double* rho) try {
   if (int rc = bind(c)) return rc;
   if (int rc = check_window(c, B)) return rc;
   if (!rho) return fail(QMPS_ERR_ARG, "null rho");
-  if (!c->have_env) return fail(QMPS_ERR_STATE, "no resident environment");
+  if (!c->env.covers(c->window, c->window + B)) return fail(QMPS_ERR_STATE, "no resident environment for the window [%lld, %lld)", (long long)c->window, (long long)(c->window + B));
   if (!c->d_rho) HIP_TRY(hipMalloc(&c->d_rho, (size_t)c->max_batch * 256));
   // recompute from the resident (A, r): the energy-only kernel writes rho when asked to
   c->want_rho = true;
@@ -460,7 +496,9 @@ int cell2_run(qmps_ctx* c, int64_t B, int n_terms, int max_iter, double tol, dou
   c->partials_B = -1;
   HIP_TRY(qmps::launch_cell2(c->D, a, c->stream));
   c->n_states = 0;  // the resident single-site states (if any) are no longer what d_E refers to
-  c->have_env = false;
+  forget_results(c);
+  c->energies.add(0, B);      // the unit cell's own energies, iteration counts and statuses, at the start of the buffers
+  c->counts.add(0, B);
   return qmps_get_energies(c, B, E_out, iters_out, status_out);
 }
 }  // namespace

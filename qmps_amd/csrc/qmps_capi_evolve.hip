@@ -604,6 +604,7 @@ int evolve_bfgs_group(const BfgsGroup& job) {
   memcpy(job.params, run.X.data(), TP * sizeof(double));
   if (job.hinv) memcpy(job.hinv, run.Hinv.data(), TP * P * sizeof(double));
   if (job.counters_out) { job.counters_out[0] = run.n_grad; job.counters_out[1] = run.n_ladder; job.counters_out[2] = run.nfev; job.counters_out[3] = run.grad_ms; }
+  forget_resident_candidates(c);
   return QMPS_OK;
 }
 
@@ -822,7 +823,7 @@ int qmps_evolve_bfgs_device(qmps_ctx* c, int64_t T, int kind, int n_params, doub
     for (int64_t t = 0; t < T; ++t) { a0 += nfev[t]; a1 += nfail[t]; a3 += nfev[T + t]; }
     counters_out[0] = a0; counters_out[1] = a1; counters_out[2] = ms; counters_out[3] = a3;
   }
-  forget_resident_state(c);
+  forget_resident_candidates(c);
   c->grad_warm_T = 0;
   return QMPS_OK;
 }

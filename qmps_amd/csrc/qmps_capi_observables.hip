@@ -22,7 +22,7 @@ int resident_front(qmps_ctx* c, int64_t B, uint64_t bytes_per_eval, const char* 
                 (unsigned long long)bytes_per_eval, other_axis);
   if (c->window + B > c->n_states)
     return fail(QMPS_ERR_STATE, "window [%lld, %lld) but only %lld states are resident", (long long)c->window, (long long)(c->window + B), (long long)c->n_states);
-  if (!c->have_env) return fail(QMPS_ERR_STATE, "no resident environment: run qmps_energy_launch (without QMPS_FLAG_NO_ENV_OUT) or qmps_set_env_guess first");
+  if (!c->env.covers(c->window, c->window + B)) return fail(QMPS_ERR_STATE, "no resident environment for the window: run qmps_energy_launch (without QMPS_FLAG_NO_ENV_OUT) or qmps_set_env_guess first");
   empty = B == 0;
   return QMPS_OK;
 }

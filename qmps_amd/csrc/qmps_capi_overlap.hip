@@ -240,7 +240,11 @@ int qmps_overlap_launch(qmps_ctx* c, int64_t B, int max_rounds, double tol, int 
     c->active_n = 0;
   }
   if (int rc = launch_overlap_kernels(c, a)) return rc;
-  c->have_env = false;
+  forget_environments(c);
+  c->counts.remove(c->window, c->window + B);     // the window's iteration counts and statuses are this launch's now
+  c->overlap_vals.add(c->window, c->window + B);
+  if (want_r) c->overlap_x.add(c->window, c->window + B);
+  else c->overlap_x.remove(c->window, c->window + B);     // (the slots keep the fixed points of an earlier launch: a start, not this launch's result)
   c->have_guess = false;
   if (want_r) {                 // (a launch that keeps no fixed points leaves the resident ones alone)
     c->have_overlap_x = true;
@@ -257,9 +261,12 @@ int qmps_overlap_get(qmps_ctx* c, int64_t B, double* eta_out, double* r_out, int
   if (int rc = check_window(c, B)) return rc;
   if (!eta_out) return fail(QMPS_ERR_ARG, "null eta_out");
   if (!c->d_eta) return fail(QMPS_ERR_STATE, "qmps_overlap_launch has not been called");
+  if (B > 0 && !c->overlap_vals.covers(c->window, c->window + B))
+    return fail(QMPS_ERR_STATE, "no overlap results resident for the window [%lld, %lld): no qmps_overlap_launch has covered it since the candidates were set", (long long)c->window, (long long)(c->window + B));
   HIP_TRY(hipMemcpyAsync(eta_out, (char*)c->d_eta + (size_t)c->window * 16, (size_t)B * 16, hipMemcpyDeviceToHost, c->stream));
   if (r_out) {
-    if (!c->have_overlap_x) return fail(QMPS_ERR_STATE, "the last overlap launch did not keep the fixed points (QMPS_OVERLAP_WANT_R)");
+    if (!c->have_overlap_x || (B > 0 && !c->overlap_x.covers(c->window, c->window + B)))
+      return fail(QMPS_ERR_STATE, "the last overlap launch over the window did not keep the fixed points (QMPS_OVERLAP_WANT_R)");
     HIP_TRY(hipMemcpyAsync(r_out, win_r(c), (size_t)B * env_bytes(c), hipMemcpyDeviceToHost, c->stream));
   }
   if (rounds_out) HIP_TRY(hipMemcpyAsync(rounds_out, win_iters(c), (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
@@ -274,6 +281,8 @@ int qmps_overlap_get_objective(qmps_ctx* c, int64_t B, double* f_out) try {
   if (int rc = check_window(c, B)) return rc;
   if (!f_out) return fail(QMPS_ERR_ARG, "null f_out");
   if (!c->d_f) return fail(QMPS_ERR_STATE, "qmps_overlap_launch has not been called");
+  if (B > 0 && !c->overlap_vals.covers(c->window, c->window + B))
+    return fail(QMPS_ERR_STATE, "no overlap results resident for the window [%lld, %lld): no qmps_overlap_launch has covered it since the candidates were set", (long long)c->window, (long long)(c->window + B));
   HIP_TRY(hipMemcpyAsync(f_out, c->d_f + c->window, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return QMPS_OK;

@@ -96,6 +96,7 @@ int whole_run(qmps_ctx* c, const RotoRun& r, hipError_t (*launch)(int, const qmp
   HIP_TRY(launch(r.kind, ra, c->stream));
   HIP_TRY(qmps::launch_ansatz(c->D, r.kind, r.base, r.P, c->d_A, r.R, c->stream));
   c->n_states = r.R; c->ans_have = false; c->tensors_valid = true;
+  forget_results(c);      // the launch below states what the R final vectors leave resident
   return qmps_energy_launch(c, r.R, r.max_iter, r.tol, c->default_solver);
 }
 
@@ -154,7 +155,8 @@ int step_by_step(qmps_ctx* c, const RotoRun& r) {
   // the capture: the R final parameter vectors, their energies / statuses / environments
   c->n_states = r.R;
   c->window = 0;
-  c->have_env = true;
+  forget_results(c);
+  c->env.add(0, r.R); c->env_start.add(0, r.R); c->energies.add(0, r.R); c->counts.add(0, r.R);
   c->partials_B = -1;
   c->acc_pending = false;
   if (fused) {
@@ -246,6 +248,7 @@ int evolve_run(qmps_ctx* c, const RotoRun& r, int n_steps, size_t slot_bytes, do
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->window = 0;
   forget_resident_state(c);
+  c->energies.clear();        // d_E is the run's objective buffer: what qmps_get_energies would return are overlap objectives
   c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
   auto evaluate = [&](int shifts) -> int {      // shifts = nsh: the shifted batch of parameter *idx;  0: the T base vectors
     const int64_t n = shifts > 0 ? (int64_t)shifts * T : T;

@@ -22,6 +22,7 @@
 #include <chrono>
 #include <cmath>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "qmps_hip.h"
@@ -64,6 +65,49 @@ constexpr int kSumBlocks = 256;
     ncclResult_t r_ = (expr);                                                                                    \
     if (r_ != ncclSuccess) return qmps_host::fail(QMPS_ERR_RCCL, "%s failed: %s", #expr, ncclGetErrorString(r_)); \
   } while (0)
+
+// Which evaluations of a resident array hold what a context-wide flag used to claim for all of them: a short list of disjoint
+// half-open intervals [lo, hi), sorted.  Launches and read-backs are windowed (qmps_set_window), so the facts about d_r, d_E, d_iters
+// and d_status are kept per slot: a launch adds its window, a call that overwrites or outdates slots removes them.
+struct qmps_slots {
+  std::vector<std::pair<int64_t, int64_t>> v;
+  void clear() { v.clear(); }
+  bool any() const { return !v.empty(); }
+  bool touches(int64_t lo, int64_t hi) const {
+    for (const auto& s : v)
+      if (s.second > lo && s.first < hi) return true;
+    return false;
+  }
+  void remove(int64_t lo, int64_t hi) {
+    if (hi <= lo || !touches(lo, hi)) return;      // (the common case on the hot path: nothing to do, nothing allocated)
+    std::vector<std::pair<int64_t, int64_t>> out;
+    for (const auto& s : v) {
+      if (s.second <= lo || s.first >= hi) { out.push_back(s); continue; }
+      if (s.first < lo) out.push_back({s.first, lo});
+      if (s.second > hi) out.push_back({hi, s.second});
+    }
+    v.swap(out);
+  }
+  void add(int64_t lo, int64_t hi) {
+    if (hi <= lo || covers(lo, hi)) return;        // (a step repeated over the same window: nothing to do, nothing allocated)
+    for (const auto& s : v) {          // swallow what touches [lo, hi)
+      if (s.second < lo || s.first > hi) continue;
+      if (s.first < lo) lo = s.first;
+      if (s.second > hi) hi = s.second;
+    }
+    remove(lo, hi);
+    size_t at = 0;
+    while (at < v.size() && v[at].first < lo) ++at;
+    v.insert(v.begin() + at, {lo, hi});
+  }
+  // an empty range is covered as soon as anything is resident (B = 0 calls keep the answer of the old flag)
+  bool covers(int64_t lo, int64_t hi) const {
+    if (hi <= lo) return any();
+    for (const auto& s : v)
+      if (s.first <= lo && hi <= s.second) return true;
+    return false;
+  }
+};
 
 struct qmps_ctx {
   int device = -1;
@@ -164,7 +208,13 @@ struct qmps_ctx {
   int64_t window = 0;               // first evaluation addressed by the launch / read-back calls (qmps_set_window)
   int64_t overlap_refs = 0;         // reference tensors resident for the overlap objective (1 = shared by the batch)
   bool have_guess = false;
-  bool have_env = false;
+  qmps_slots env;                   // d_r holds environments the read-backs may return: stored by an energy launch, or given by qmps_set_env_guess
+  qmps_slots env_guessed;           // ... of which given by qmps_set_env_guess and not yet replaced by a solve's result
+  qmps_slots env_start;             // d_r holds something a solve may start from: `env`, and a guess under a launch with QMPS_FLAG_NO_ENV_OUT
+  qmps_slots energies;              // d_E holds energies of the resident states under the resident number of terms
+  qmps_slots counts;                // d_iters / d_status were written by the energy launch that wrote those energies (not by an overlap launch)
+  qmps_slots overlap_vals;          // d_eta / d_f / d_iters / d_status hold an overlap launch's results for the resident candidates
+  qmps_slots overlap_x;             // d_r holds the fixed points of THAT launch (have_overlap_x: of some launch - enough for a warm start)
   bool have_overlap_x = false;       // d_r holds the fixed points of the last overlap launch (QMPS_OVERLAP_WANT_R)
   bool want_rho = false;
   bool defer_sync = false;          // one-shot entry points: the setters leave their H2D copies in flight, ONE synchronisation at the end
@@ -278,9 +328,22 @@ inline int krylov_after() {
 int bind(qmps_ctx* c);
 // after an overlap or evolve call: the energy path's resident environments, guesses, fixed points, pending cost and per-wave partial
 // sums no longer describe the buffers
+inline void forget_environments(qmps_ctx* c) { c->env.clear(); c->env_guessed.clear(); c->env_start.clear(); }
+// a new upload: nothing that was computed describes the resident states
+inline void forget_results(qmps_ctx* c) { forget_environments(c); c->energies.clear(); c->counts.clear(); c->overlap_vals.clear(); c->overlap_x.clear(); }
 inline void forget_resident_state(qmps_ctx* c) {
-  c->have_env = false; c->have_guess = false; c->have_overlap_x = false; c->acc_pending = false; c->partials_B = -1;
+  forget_environments(c); c->counts.clear(); c->overlap_vals.clear(); c->overlap_x.clear();     // (the overlap and evolve launches write d_iters / d_status, d_eta and d_f)
+  c->have_guess = false; c->have_overlap_x = false; c->acc_pending = false; c->partials_B = -1;
 }
+// What the BFGS evolve drivers leave: no resident candidates (the last batch was a ladder, a gradient batch or - device-resident drivers - none
+// at all) and none of their results; the fixed points of the last gradient batch stay where QMPS_BFGS_WARM looks for them (grad_warm_T)
+inline void forget_resident_candidates(qmps_ctx* c) {
+  forget_resident_state(c);
+  c->n_states = 0; c->window = 0; c->tensors_valid = false;
+  c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
+}
+// the window's slots of d_r as the start of a solve: only where something was put there
+inline bool window_has_start(const qmps_ctx* c, int64_t B) { return c->env_start.covers(c->window, c->window + B); }
 inline size_t tensor_bytes(const qmps_ctx* c) { return (size_t)32 * c->D * c->D; }
 inline size_t env_bytes(const qmps_ctx* c) { return (size_t)16 * c->D * c->D; }
 int ensure_scratch(qmps_ctx* c, size_t bytes);

@@ -237,9 +237,15 @@ class EnergyEngine:
         `set_exchange_period`."""
         L.check(self._lib.qmps_sync(self._ctx))
 
-    def results(self, B=None):
+    def results(self, B=None, counts=True):
+        """(E (B, n_terms), iterations (B,), status (B,)) of the energy launch over the window.  counts=False: (E, None, None) - the
+        energies of `launch_energy_only` over states no launch has solved come with no iteration counts or statuses, and the
+        library refuses to pair them with another launch's."""
         B = self.B if B is None else B
         E = np.empty((B, self.n_terms))
+        if not counts:
+            L.check(self._lib.qmps_get_energies(self._ctx, B, _f64(E), None, None))
+            return E, None, None
         it = np.empty(B, dtype=np.int32)
         st = np.empty(B, dtype=np.int32)
         L.check(self._lib.qmps_get_energies(self._ctx, B, _f64(E), _i32(it), _i32(st)))
