@@ -10,6 +10,9 @@
 // One workgroup of N x N threads per evaluation (N = 4: four evaluations per wave), thread (i, j) owns entry [i][j]:
 //   X = -i/2 sum_k p_k G_k  (entries read straight off the parameter vector), scaled by 2^-s so that ||X||_F <= 1/4,
 //   T = Taylor polynomial of degree 13 by Horner's rule (12 products, truncation error < 1e-19), s squarings.
+// Every evaluation has its OWN exponent s: a unitary never depends on the evaluations beside it (each needless squaring doubles the
+// rounding error, and at N = 4 one row of size 1e5 used to cost its three workgroup-mates eight digits).  Only the bound of the squaring loop
+// is the workgroup's largest s, for the barriers; an evaluation that has finished its squarings carries its tile over unchanged.
 // Products through padded LDS tiles.  Output: the full unitary (qmps_su_unitaries, the two-site unit cell) or directly the
 // state tensor A[s][i][j] = U[2 i + s][j], j < D (unitary_to_tensor, qmps/tools.py:151-154, fused).
 #include <hip/hip_runtime.h>
@@ -28,7 +31,7 @@ __global__ __launch_bounds__((N * N < 64) ? 64 : N * N) void su_exp_kernel(const
   constexpr int NN = N * N, P = N + 1, THREADS = NN < 64 ? 64 : NN, ITEMS = THREADS / NN, WAVES = THREADS / 64;
   __shared__ double2 sXm[ITEMS][N][P], sT[2][ITEMS][N][P];
   __shared__ double red[WAVES > 1 ? WAVES : 1];
-  __shared__ int s_scale;
+  __shared__ int s_scale, s_item[ITEMS];
   const int tid = threadIdx.x, e = tid / NN, l = tid % NN, i = l / N, j = l % N;
   const int64_t b = (int64_t)blockIdx.x * ITEMS + e;
   const int64_t bb = b < B ? b : B - 1;           // surplus lanes of the last workgroup shadow a real evaluation
@@ -51,7 +54,7 @@ __global__ __launch_bounds__((N * N < 64) ? 64 : N * N) void su_exp_kernel(const
     }
     x = make_double2(0.0, -0.5 * d);
   }
-  // ---- scaling: ||X||_F 2^-s <= 1/4 (the workgroup's largest s serves all of its evaluations)
+  // ---- scaling: ||X||_F 2^-s <= 1/4, s per evaluation; s_scale = the workgroup's largest s bounds the squaring loop
   {
     double f2 = x.x * x.x + x.y * x.y;
     if constexpr (NN == 16) f2 = row16_sum(f2);
@@ -69,10 +72,13 @@ __global__ __launch_bounds__((N * N < 64) ? 64 : N * N) void su_exp_kernel(const
     int s = 0;
     if (fro > 0.25) s = (int)ceil(log2(fro * 4.0));
     if (s > 60) s = 60;
-    if (l == 0) atomicMax(&s_scale, s);
+    if (l == 0) {
+      s_item[e] = s;
+      atomicMax(&s_scale, s);
+    }
     __syncthreads();
   }
-  const int s = s_scale;
+  const int s = s_item[e], s_max = s_scale;
   const double sc = ldexp(1.0, -s);
   x.x *= sc;
   x.y *= sc;
@@ -92,11 +98,13 @@ __global__ __launch_bounds__((N * N < 64) ? 64 : N * N) void su_exp_kernel(const
     sT[cur][e][i][j] = t;
     __syncthreads();
   }
-  for (int q2 = 0; q2 < s; ++q2) {
-    double2 acc = make_double2(0.0, 0.0);
+  for (int q2 = 0; q2 < s_max; ++q2) {
+    if (q2 < s) {
+      double2 acc = make_double2(0.0, 0.0);
 #pragma unroll 8
-    for (int q = 0; q < N; ++q) cfma(sT[cur][e][i][q], sT[cur][e][q][j], acc);
-    t = acc;
+      for (int q = 0; q < N; ++q) cfma(sT[cur][e][i][q], sT[cur][e][q][j], acc);
+      t = acc;
+    }
     cur ^= 1;
     sT[cur][e][i][j] = t;
     __syncthreads();

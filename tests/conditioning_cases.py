@@ -61,7 +61,7 @@ def near_product_tensors(rng, D, t, n, gauge=True):
 def _mp_apply(A, r, D):
     """T(r) = sum_s A_s r A_s^H on lists of mpc."""
     out = [[mp.mpc(0) for _ in range(D)] for _ in range(D)]
-    for s in range(2):
+    for s in range(len(A)):
         As = A[s]
         Ac = [[As[i][j].conjugate() for j in range(D)] for i in range(D)]
         X = [[mp.fdot(As[i], [r[k][l] for k in range(D)]) for l in range(D)] for i in range(D)]       # A_s r
@@ -79,7 +79,7 @@ def reference_mp(A):
         M = O.transfer_matrix(A) - np.eye(N)
         M[N - 1, :] += np.eye(D).reshape(N)
         lu = scipy.linalg.lu_factor(M)
-        Amp = [[[mp.mpc(A[s, i, j]) for j in range(D)] for i in range(D)] for s in range(2)]
+        Amp = [[[mp.mpc(A[s, i, j]) for j in range(D)] for i in range(D)] for s in range(A.shape[0])]
         r = [[mp.mpc(0) for _ in range(D)] for _ in range(D)]
         for _ in range(12):
             Tr = _mp_apply(Amp, r, D)
