@@ -80,7 +80,8 @@ extern "C" {
 /* DIRECT fixed-point solve (D = 2, 4 and 8; D = 16 runs QMPS_ENV_POWER_SQUARING): what the reference itself
  * does at qmps/tools.py:176-182 - an exact solve, not an iteration.  For a left isometry the transfer map preserves
  * the trace, so the environment solves the real D^2 x D^2 linear system (R - 1 + e t^T) u = e (R: the map in real
- * coordinates of the Hermitian r, t: trace functional), done by Gauss-Jordan elimination in registers.  The result is
+ * coordinates of the Hermitian r, t: trace functional), done by elimination without pivoting in registers (Gauss-Jordan;
+ * at D = 4 LU elimination and back substitution).  The result is
  * ACCEPTED only if one power step moves it by less than tol (||T(r)/tr - r||_F < tol: the very criterion of the
  * iterative solvers, so `status` keeps its meaning); an evaluation that fails the test (tensor not an isometry,
  * degenerate transfer spectrum) continues inside the same launch with the power method 2^m steps at a time from

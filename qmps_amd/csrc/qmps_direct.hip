@@ -3,8 +3,10 @@
 // energy_direct_d4_kernel: D = 4, ONE DPP QUAD (4 lanes) PER EVALUATION, 16 evaluations per wave.  Per evaluation:
 //   tensor (512 B, read once from HBM as part of the wave's contiguous 8 KB slab -> padded LDS tile)
 //   -> the real 16 x 16 transfer matrix R, four rows per lane
-//   -> (R - 1 + e_15 t^T) u = e_15 by Gauss-Jordan elimination in registers, pivot rows handed round the quad by
-//      v_mov_b32_dpp quad_perm (VALU only; no LDS, no cross-quad traffic)
+//   -> (R - 1 + e_15 t^T) u = e_15 by LU elimination in registers - the pivots go round the quad (lane k % 4, register k / 4), so only the
+//      rows below the pivot are eliminated, in every lane alike - and back substitution by columns, whose broadcasts leave all sixteen
+//      coordinates in every lane; pivot rows and unknowns handed round the quad by v_mov_b32_dpp quad_perm (VALU only; no LDS, no
+//      cross-quad traffic)
 //   -> one power step as acceptance test (||T(r) - r||_F < tol; else the power method 2^m steps at a time); the cold start keeps its two
 //      halves W_00, W_11 (W_{t2 s2} = A_t2 r A_s2^+, T(r) = W_00 + W_11) and forms W_01 / W_10 where rho needs them
 //   -> LDL^H positive-definiteness test, two-site density matrix - of its upper triangle the real and imaginary parts that some
@@ -35,34 +37,10 @@ struct QuadOps {
   using P = bool;
   int q;                  // row index of this lane inside its quad
   const double2* row;     // the evaluation's tensor in LDS: A_s[i][j] = row[(4 s + i) 4 + j]
-  double* gj;             // QMPS_GJ_LDS: the quad's 16-double strip for the pivot rows of the elimination
   __device__ __forceinline__ P q_eq(int i) const { return q == i; }
   __device__ __forceinline__ P q_gt(int i) const { return q > i; }
   template <int L>
   static __device__ __forceinline__ V bcast(V v) { return quad_bcast<L>(v); }
-  template <int L, int K>
-  __device__ __forceinline__ void row_bcast(const V (&r)[16], V (&out)[16]) const {
-#ifdef QMPS_GJ_LDS
-    // through LDS: the owner lane parks the rest of its row, every lane of the quad reads it back (one address per quad:
-    // a broadcast read); the LDS pipe works beside the vector ALU, which the DPP moves (2 per double) keep busy
-    constexpr int K0 = K & ~1;
-    __builtin_amdgcn_wave_barrier();
-    if (q == L) {
-#pragma unroll
-      for (int j = K0; j < 16; j += 2) *(double2*)&gj[j] = make_double2(r[j], r[j + 1]);
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int j = K0; j < 16; j += 2) {
-      const double2 t = *(const double2*)&gj[j];
-      if (j >= K) out[j] = t.x;
-      out[j + 1] = t.y;
-    }
-#else
-#pragma unroll
-    for (int j = K; j < 16; ++j) out[j] = quad_bcast<L>(r[j]);
-#endif
-  }
   static __device__ __forceinline__ V qsum(V v) { return quad_sum(v); }
   static __device__ __forceinline__ V qmax(V v) {
     v = fmax(v, quad_perm<0xB1>(v));
@@ -230,9 +208,6 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
   // reads one address (rows of the partner index) and when its lanes read their own rows (64 B apart)
   __shared__ __attribute__((aligned(16))) unsigned char lds[ITEMS * PAD];
   __shared__ double sq_img[kSqDoubles];      // the rare path's 16 x 16 image
-#ifdef QMPS_GJ_LDS
-  __shared__ __attribute__((aligned(16))) double gjbuf[ITEMS * 18];     // 144-byte stride: the 16 quads on disjoint banks
-#endif
   const int lane = threadIdx.x, e = lane >> 2, q = lane & 3;
   const int64_t first = (int64_t)blockIdx.x * ITEMS;
   const int64_t b = first + e;
@@ -299,11 +274,7 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
     }
   }
   __syncthreads();
-#ifdef QMPS_GJ_LDS
-  const QuadOps o{q, (const double2*)(lds + e * PAD), gjbuf + e * 18};
-#else
-  const QuadOps o{q, (const double2*)(lds + e * PAD), nullptr};
-#endif
+  const QuadOps o{q, (const double2*)(lds + e * PAD)};
   const double tol2 = p.tol * p.tol;
 
   // ---- environment: direct solve, accepted by one power step ----
@@ -338,10 +309,12 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
     Core::build(o, Rc);
     __builtin_amdgcn_sched_barrier(0);     // phase by phase: keeps the operand reads of later phases out of the register file
     double pivmax;
-    Core::solve(o, Rc, xs, pivmax);
-    __builtin_amdgcn_sched_barrier(0);
-    Core::normalise(o, xs);
-    Core::gather(xs, us);
+    {
+      double ur[16];
+      Core::solve_gathered(o, Rc, ur, pivmax);
+      __builtin_amdgcn_sched_barrier(0);
+      Core::normalise_gathered(o, ur, us, xs);
+    }
     double d2;
     if constexpr (WARM) d2 = Core::power_step(o, xs, us, y);
     else d2 = Core::power_step_sites(o, xs, us, p.rho_need, y, W);
@@ -498,7 +471,7 @@ __global__ __launch_bounds__(64, LEAN ? QMPS_ENERGY_ONLY_LEAN_WAVES : 2) void en
       *(double2*)(lds + (off / ROW) * PAD + (off % ROW)) = v[c];
     }
     __syncthreads();
-    const QuadOps o{q, (const double2*)(lds + e * PAD), nullptr};
+    const QuadOps o{q, (const double2*)(lds + e * PAD)};
     Core::normalise(o, x);
     double us[16];
     double pre[4][4], pim[4][4], bre[4][4], bim[4][4];
