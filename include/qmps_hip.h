@@ -198,6 +198,7 @@ int qmps_abi_version(void);
  *      Added later without a bump (detect them by the symbol's presence): qmps_correlators, the two-point functions of the resident states;
  *      qmps_entanglement, their Schmidt spectra and entanglement entropies; qmps_correlator_sums, the sums over all distances of their
  *      connected two-point functions (structure factors).
+ *      qmps_correlator_sums_two_site, the same sums for two-site operators (energy-density structure factors, the energy variance per site).
  *      Changed later without a bump (same signatures; nothing a caller can detect beforehand, a refusal is an error code):
  *      RESIDENT RESULTS (below): the context knows per evaluation slot, not per context, what its buffers hold, and read-backs that used to return
  *      whatever the buffer held now fail with QMPS_ERR_STATE (same signatures).  qmps_get_env, qmps_get_rdm, qmps_energy_only_launch, qmps_correlators,
@@ -455,6 +456,27 @@ int qmps_correlator_sums(qmps_ctx* ctx, int64_t B, int n_ops, const double* ops 
                          double* G_out    /* [B][n_z][n_ops][n_ops] complex128 */,
                          double* one_out  /* nullable, [B][n_ops] complex128 */,
                          double* site_out /* nullable, [B][n_ops][n_ops] complex128 */);
+
+/* The same sums for TWO-SITE operators (4 x 4, index 2 s1 + s2 with s1 the left site, as h of qmps_set_hamiltonian); the contract of
+ * qmps_correlator_sums holds word for word - arguments, limits, refusals, NaN rules, one kernel launch and one synchronisation,
+ * nothing resident changes - with these definitions in place of the one-site ones (o[t1][t2][s1][s2] = O[2 t1 + t2][2 s1 + s2]):
+ *   E2_O(x) = sum o[t1 t2 s1 s2] A_s1 A_s2 x A_t2^+ A_t1^+      L_a = sum o_a[t1 t2 s1 s2] A_t2^+ A_t1^+ A_s1 A_s2
+ *   one[b][a]        = tr(E2_(O_a)(r)) / tau                     = <O_a(0,1)>
+ *   G[b][j][a][c]    = z_j^2 tr(L_a (1 - z_j Tt)^(-1)(b_c)) / tau,   b_c = E2_(O_c)(r) - one[c] r
+ *                    = sum_(n >= 2) z_j^n (<O_a(0,1) O_c(n,n+1)> - one[a] one[c])      (r the exact fixed point, |z| <= 1)
+ *   near[b][a][c][0] = tr(E2_(O_a O_c)(r)) / tau                 (the 4 x 4 matrix product: distance 0)
+ *   near[b][a][c][1] = <(O_a (x) 1)(1 (x) O_c)> on sites 0, 1, 2    (O_c one site to the right)
+ *   near[b][a][c][2] = <(1 (x) O_a)(O_c (x) 1)> on sites -1, 0, 1   (O_c one site to the left; the supports overlap, the order matters)
+ * The structure factor of two-site operators is composed by the caller:
+ *   S_ac(k) = sum_(q = 0, 1, 2) w_q (near[a][c][q] - one[a] one[c]) + G_ac(z) + G_ca(conj z),   w = (1, z, conj z),  z = e^(-ik);
+ * the energy variance per site of a Hermitian term h, lim (<H^2> - <H>^2) / N for H = sum_n h(n, n+1), is Re S_hh(0): zero exactly on
+ * eigenstates.  The same kernels as qmps_correlator_sums run with another source for the right-hand sides and the left vectors; the
+ * three-site expectations cost O(D^3) per operator pair and are computed by the z_0 item alone. */
+int qmps_correlator_sums_two_site(qmps_ctx* ctx, int64_t B, int n_ops, const double* ops /* [n_ops][4][4] complex128 */,
+                                  int n_z, const double* z /* [n_z] complex128 */,
+                                  double* G_out    /* [B][n_z][n_ops][n_ops] complex128 */,
+                                  double* one_out  /* nullable, [B][n_ops] complex128 */,
+                                  double* near_out /* nullable, [B][n_ops][n_ops][3] complex128 */);
 
 /* ---- one-shot host-buffer convenience (SURVEY 8(b) energy_batch / env_batch) ------------ */
 int qmps_energy_batch(qmps_ctx* ctx, int64_t B, const double* states, int kind, const double* h, int n_terms,

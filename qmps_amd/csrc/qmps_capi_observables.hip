@@ -1,5 +1,5 @@
 // qmps_capi_observables.hip - C-ABI of the observables of the resident states: two-point functions (kernels: qmps_correlator.hip),
-// Schmidt spectra and entropies (qmps_entanglement.hip), correlator sums (qmps_corrsum.hip).  Every call checks its own arguments,
+// Schmidt spectra and entropies (qmps_entanglement.hip), correlator sums of one-site and of two-site operators (qmps_corrsum.hip).  Every call checks its own arguments,
 // passes the shared front, carves its regions out of the scratch buffer, uploads its inputs, launches ONE kernel, reads its results
 // back and synchronises ONE time.  A refused call writes nothing and allocates nothing.
 #include "qmps_ctx.h"
@@ -55,6 +55,63 @@ struct ScratchLayout {
   }
   void align(size_t a) { bytes = (bytes + a - 1) / a * a; }
 };
+
+// qmps_correlator_sums and qmps_correlator_sums_two_site: one contract, one body.  `two_site`: operators of 4 x 4 entries, three
+// near values per pair where the one-site call has one `site` value, the two-site kernels.
+int correlator_sums_call(qmps_ctx* c, int64_t B, int n_ops, const double* ops, int n_z, const double* z, double* G_out, double* one_out,
+                         double* site_out, bool two_site) {
+  if (!c) return fail(QMPS_ERR_ARG, "null context");
+  if (!ops) return fail(QMPS_ERR_ARG, "null ops");
+  if (!z) return fail(QMPS_ERR_ARG, "null z");
+  if (!G_out) return fail(QMPS_ERR_ARG, "null G_out");
+  if (int rc = check_n_ops(n_ops)) return rc;
+  if (n_z < 1 || n_z > 1024) return fail(QMPS_ERR_ARG, "n_z=%d outside [1, 1024]", n_z);
+  for (int j = 0; j < n_z; ++j) {
+    const double n2 = z[2 * j] * z[2 * j] + z[2 * j + 1] * z[2 * j + 1];
+    // (the slack is for e^(ik) as float64 rounds it; a NaN fails the comparison too)
+    if (!(n2 <= 1.0 + 1e-12)) return fail(QMPS_ERR_ARG, "|z[%d]|^2 = %.17g outside the closed unit disc: the sum over n does not converge there", j, n2);
+  }
+  const uint64_t per_eval = (uint64_t)n_z * n_ops * n_ops * 16;
+  bool empty = false;
+  if (int rc = resident_front(c, B, per_eval, "z", empty)) return rc;
+  if (empty) return QMPS_OK;
+  if (int rc = ensure_tensors(c)) return rc;
+  const int64_t slabs = qmps::correlator_sums_slabs(c->D, B * n_z);
+  const size_t z_bytes = (size_t)n_z * 16, G_bytes = (size_t)B * per_eval, one_bytes = (size_t)B * n_ops * 16, site_bytes = one_bytes * n_ops * (two_site ? 3 : 1);
+  ScratchLayout s;
+  const size_t ops_at = s.take(two_site ? 1024 : 256), z_at = s.take(16384), G_at = s.take(G_bytes), one_at = s.take(one_bytes), site_at = s.take(site_bytes);
+  // D = 16: the matrices of the workgroups, (G_bytes + one_bytes + site_bytes + 255) / 256 * 256 bytes behind G (the operators and z
+  // take multiples of 256 bytes, so rounding the offset is rounding that sum)
+  s.align(256);
+  const size_t work_at = s.take((size_t)slabs * qmps::correlator_sums_slab_bytes());
+  if (int rc = ensure_scratch(c, s.bytes)) return rc;
+  char* base = (char*)c->d_scratch;
+  char *d_ops = base + ops_at, *d_z = base + z_at, *d_G = base + G_at, *d_one = base + one_at, *d_site = base + site_at;
+  HIP_TRY(hipMemcpyAsync(d_ops, ops, (size_t)n_ops * (two_site ? 256 : 64), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_z, z, z_bytes, hipMemcpyHostToDevice, c->stream));
+  qmps::CorrSumArgs a{};
+  a.A = win_A(c);
+  a.r = win_r(c);
+  a.ops = d_ops;
+  a.z = d_z;
+  a.G = d_G;
+  a.one = one_out ? d_one : nullptr;
+  a.site = site_out ? d_site : nullptr;
+  a.work = slabs > 0 ? base + work_at : nullptr;
+  a.B = B;
+  a.n_ops = n_ops;
+  a.n_z = n_z;
+  a.n_slabs = (int)slabs;
+  if (int rc = two_site ? timed_launch(c, "correlator_sums_two_site", qmps::launch_correlator_sums_two_site, a)
+                        : timed_launch(c, "correlator_sums", qmps::launch_correlator_sums, a))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(G_out, d_G, G_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (one_out) HIP_TRY(hipMemcpyAsync(one_out, d_one, one_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (site_out) HIP_TRY(hipMemcpyAsync(site_out, d_site, site_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return QMPS_OK;
+}
+
 
 }  // namespace
 
@@ -124,54 +181,13 @@ QMPS_API_CATCH
 
 int qmps_correlator_sums(qmps_ctx* c, int64_t B, int n_ops, const double* ops, int n_z, const double* z, double* G_out, double* one_out,
                          double* site_out) try {
-  if (!c) return fail(QMPS_ERR_ARG, "null context");
-  if (!ops) return fail(QMPS_ERR_ARG, "null ops");
-  if (!z) return fail(QMPS_ERR_ARG, "null z");
-  if (!G_out) return fail(QMPS_ERR_ARG, "null G_out");
-  if (int rc = check_n_ops(n_ops)) return rc;
-  if (n_z < 1 || n_z > 1024) return fail(QMPS_ERR_ARG, "n_z=%d outside [1, 1024]", n_z);
-  for (int j = 0; j < n_z; ++j) {
-    const double n2 = z[2 * j] * z[2 * j] + z[2 * j + 1] * z[2 * j + 1];
-    // (the slack is for e^(ik) as float64 rounds it; a NaN fails the comparison too)
-    if (!(n2 <= 1.0 + 1e-12)) return fail(QMPS_ERR_ARG, "|z[%d]|^2 = %.17g outside the closed unit disc: the sum over n does not converge there", j, n2);
-  }
-  const uint64_t per_eval = (uint64_t)n_z * n_ops * n_ops * 16;
-  bool empty = false;
-  if (int rc = resident_front(c, B, per_eval, "z", empty)) return rc;
-  if (empty) return QMPS_OK;
-  if (int rc = ensure_tensors(c)) return rc;
-  const int64_t slabs = qmps::correlator_sums_slabs(c->D, B * n_z);
-  const size_t z_bytes = (size_t)n_z * 16, G_bytes = (size_t)B * per_eval, one_bytes = (size_t)B * n_ops * 16, site_bytes = one_bytes * n_ops;
-  ScratchLayout s;
-  const size_t ops_at = s.take(256), z_at = s.take(16384), G_at = s.take(G_bytes), one_at = s.take(one_bytes), site_at = s.take(site_bytes);
-  // D = 16: the matrices of the workgroups, (G_bytes + one_bytes + site_bytes + 255) / 256 * 256 bytes behind G (the operators and z
-  // take multiples of 256 bytes, so rounding the offset is rounding that sum)
-  s.align(256);
-  const size_t work_at = s.take((size_t)slabs * qmps::correlator_sums_slab_bytes());
-  if (int rc = ensure_scratch(c, s.bytes)) return rc;
-  char* base = (char*)c->d_scratch;
-  char *d_ops = base + ops_at, *d_z = base + z_at, *d_G = base + G_at, *d_one = base + one_at, *d_site = base + site_at;
-  HIP_TRY(hipMemcpyAsync(d_ops, ops, (size_t)n_ops * 64, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_z, z, z_bytes, hipMemcpyHostToDevice, c->stream));
-  qmps::CorrSumArgs a{};
-  a.A = win_A(c);
-  a.r = win_r(c);
-  a.ops = d_ops;
-  a.z = d_z;
-  a.G = d_G;
-  a.one = one_out ? d_one : nullptr;
-  a.site = site_out ? d_site : nullptr;
-  a.work = slabs > 0 ? base + work_at : nullptr;
-  a.B = B;
-  a.n_ops = n_ops;
-  a.n_z = n_z;
-  a.n_slabs = (int)slabs;
-  if (int rc = timed_launch(c, "correlator_sums", qmps::launch_correlator_sums, a)) return rc;
-  HIP_TRY(hipMemcpyAsync(G_out, d_G, G_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (one_out) HIP_TRY(hipMemcpyAsync(one_out, d_one, one_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (site_out) HIP_TRY(hipMemcpyAsync(site_out, d_site, site_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return QMPS_OK;
+  return correlator_sums_call(c, B, n_ops, ops, n_z, z, G_out, one_out, site_out, false);
+}
+QMPS_API_CATCH
+
+int qmps_correlator_sums_two_site(qmps_ctx* c, int64_t B, int n_ops, const double* ops, int n_z, const double* z, double* G_out, double* one_out,
+                                  double* near_out) try {
+  return correlator_sums_call(c, B, n_ops, ops, n_z, z, G_out, one_out, near_out, true);
 }
 QMPS_API_CATCH
 

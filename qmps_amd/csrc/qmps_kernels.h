@@ -468,11 +468,11 @@ hipError_t launch_entanglement(int D, const EntanglementArgs& a, hipStream_t st)
 struct CorrSumArgs {
   const void* A;       // [B][2][D][D] complex
   const void* r;       // [B][D][D] complex right environments (any normalisation: everything is divided by tr r)
-  const void* ops;     // [n_ops][2][2] complex, O[t][s] = <t|O|s> (device)
+  const void* ops;     // [n_ops][2][2] complex, O[t][s] = <t|O|s> (device); the two-site launch: [n_ops][4][4], index 2 s1 + s2
   const void* z;       // [n_z] complex (device)
   void* G;             // [B][n_z][n_ops][n_ops] complex
   void* one;           // nullable [B][n_ops] complex: <O_a>
-  void* site;          // nullable [B][n_ops][n_ops] complex: <O_a O_c> on one site
+  void* site;          // nullable [B][n_ops][n_ops] complex: <O_a O_c> on one site; the two-site launch: [B][n_ops][n_ops][3], near
   void* work;          // D = 16 only: n_slabs x correlator_sums_slab_bytes(), one matrix per workgroup
   int64_t B;
   int n_ops, n_z;      // 1 <= n_ops <= kMaxObservableOps, n_z >= 1
@@ -482,5 +482,7 @@ constexpr int kCorrSumMaxSlabs = 252;                     // 252 slabs of 1040 K
 int64_t correlator_sums_slabs(int D, int64_t items);      // slabs the launch wants for this many (evaluation, z) items: 0 unless D = 16
 size_t correlator_sums_slab_bytes();
 hipError_t launch_correlator_sums(int D, const CorrSumArgs& a, hipStream_t st);
+// the same kernels with the two-site source (qmps_corrsum_two_site.h): G sums n >= 2, `site` takes the distances 0, +1, -1
+hipError_t launch_correlator_sums_two_site(int D, const CorrSumArgs& a, hipStream_t st);
 
 }  // namespace qmps

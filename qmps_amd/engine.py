@@ -40,6 +40,16 @@ def _one_site_ops(ops):
     return np.ascontiguousarray(ops)
 
 
+def _two_site_ops(ops):
+    """(m, 4, 4) array-like or one (4, 4) matrix -> contiguous (m, 4, 4) complex128; None for anything else"""
+    ops = np.asarray(ops, dtype=np.complex128)
+    if ops.shape == (4, 4):
+        ops = ops[None]
+    if ops.ndim != 3 or ops.shape[1:] != (4, 4):
+        return None
+    return np.ascontiguousarray(ops)
+
+
 class EnergyEngine:
     """Owns one `qmps_ctx`.  Not thread-safe; one engine per thread / device."""
 
@@ -292,18 +302,23 @@ class EnergyEngine:
         (B, n_z, m, m) complex128, by one linear solve of order D^2 per (b, j) - the resolvent of the transfer map with its fixed point
         projected out, nothing truncated.  ops as in `correlators`; z: up to 1024 complex points with |z| <= 1.  want_one_site=True adds
         one[b, a] = <O_a> (B, m), want_site=True adds site[b, a, c] = <O_a O_c> on one site (B, m, m), in this order after G.  A state
-        with a degenerate fixed point has no finite sum at |z| = 1: NaN for that (b, j) alone.  One kernel launch, one synchronisation."""
+        with a degenerate fixed point has no finite sum at |z| = 1: NaN for that (b, j) alone.  One kernel launch, one synchronisation.
+        Two-site operators - ops of shape (m, 4, 4) or one (4, 4) matrix, index 2 s1 + s2 with s1 the left site as in `set_hamiltonian` -
+        go to qmps_correlator_sums_two_site: G[b, j, a, c] = sum_(n >= 2) z_j^n (<O_a(0,1) O_c(n,n+1)> - <O_a> <O_c>), one[b, a] =
+        <O_a(0,1)>, and want_site=True adds near (B, m, m, 3) in the place of site: the overlapping distances n = 0, +1, -1
+        (near[..., 0] the 4 x 4 product on one bond, near[..., 1] O_c one site to the right of O_a, near[..., 2] one site to the left)."""
         B = self.B if B is None else int(B)
-        ops = _one_site_ops(ops)
+        two = _two_site_ops(ops)
+        ops = _one_site_ops(ops) if two is None else two
         z = np.ascontiguousarray(np.asarray(z, dtype=np.complex128).reshape(-1))
         m, n_z, n = ops.shape[0], z.shape[0], max(B, 0)
         # (the library checks the sizes before anything is written: an array it refuses is never touched)
         G = np.empty((B, n_z, m, m) if 0 <= n * n_z * m * m <= (1 << 26) else (0,), dtype=np.complex128)
         one = np.empty((n, m), dtype=np.complex128) if want_one_site else None
-        site = np.empty((n, m, m), dtype=np.complex128) if want_site else None
-        L.check(self._lib.qmps_correlator_sums(self._ctx, B, m, _f64(ops.view(np.float64)), n_z, _f64(z.view(np.float64)), _f64(G.view(np.float64)),
-                                               None if one is None else _f64(one.view(np.float64)),
-                                               None if site is None else _f64(site.view(np.float64))))
+        site = np.empty((n, m, m) if two is None else (n, m, m, 3), dtype=np.complex128) if want_site else None
+        args = (self._ctx, B, m, _f64(ops.view(np.float64)), n_z, _f64(z.view(np.float64)), _f64(G.view(np.float64)),
+                None if one is None else _f64(one.view(np.float64)), None if site is None else _f64(site.view(np.float64)))
+        L.check(self._lib.qmps_correlator_sums(*args) if two is None else self._lib.qmps_correlator_sums_two_site(*args))
         out = (G,) + ((one,) if want_one_site else ()) + ((site,) if want_site else ())
         return out if len(out) > 1 else G
 
@@ -319,8 +334,33 @@ class EnergyEngine:
         z[0::2] = np.exp(-1j * k)
         z[1::2] = np.exp(1j * k)
         G, one, site = self.correlator_sums(ops, z, B=B, want_one_site=True, want_site=True)
-        S = (site - one[:, :, None] * one[:, None, :])[:, None] + G[:, 0::2] + np.swapaxes(G[:, 1::2], -1, -2)
+        conn = one[:, :, None] * one[:, None, :]
+        if site.ndim == 4:      # two-site operators: the distances 0, +1, -1 overlap and come as `near`, weighted (1, e^(-ik), e^(+ik))
+            w = np.stack([np.ones_like(z[0::2]), z[0::2], z[1::2]], axis=-1)
+            S = np.einsum('qd,bacd->bqac', w, site - conn[..., None]) + G[:, 0::2] + np.swapaxes(G[:, 1::2], -1, -2)
+        else:
+            S = (site - conn)[:, None] + G[:, 0::2] + np.swapaxes(G[:, 1::2], -1, -2)
         return (S, one) if want_one_site else S
+
+    def energy_variance(self, h=None, B=None):
+        """Energy variance per site of the resident states, lim (<H^2> - <H>^2) / N for H = sum_n h(n, n+1): Re S_hh(0) of
+        `structure_factor` with the two-site term h, for every term - shape (B, n_terms) float64.  Zero exactly on eigenstates of H, so
+        it measures how good a variational state is, which the energy alone does not.  h: (4, 4) or (n_terms, 4, 4), by default the
+        resident Hamiltonian (`set_hamiltonian`); ValueError when there is neither.  Terms go four at a time through `correlator_sums`
+        at z = (1, 1); the diagonal is used (the variance of a sum of terms needs their cross terms: pass the sum as one term)."""
+        if h is None:
+            h = getattr(self, '_h_resident', None)
+            if h is None:
+                raise ValueError('energy_variance: no resident Hamiltonian (set_hamiltonian) and none given')
+        h = _two_site_ops(h)
+        if h is None:
+            raise ValueError('energy_variance: h of shape (n_terms, 4, 4) or (4, 4) expected')
+        B = self.B if B is None else int(B)
+        out = np.empty((max(B, 0), h.shape[0]))
+        for first in range(0, h.shape[0], 4):
+            S = self.structure_factor(h[first:first + 4], [0.0], B=B)
+            out[:, first:first + 4] = np.einsum('baa->ba', S[:, 0]).real
+        return out
 
     def entanglement(self, B=None, want_vectors=False):
         """Entanglement (Schmidt) spectra of the resident states from their resident environments (`launch` with the environments stored,

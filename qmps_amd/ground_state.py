@@ -469,7 +469,20 @@ def structure_factor(params, ops, k, D=2, state_tensor=ShallowCNOTStateTensor):
     ops: (m, 2, 2) one-site operators (or one (2, 2) matrix), m <= 4; k: momenta in radians per site.  The tensors are built on the
     device for the ansatz classes libqmps_hip knows (`device_kind`), one environment solve runs with the environments stored, and ONE
     launch solves the deflated resolvent of the transfer map for every (state, k, sign): no chain is truncated, the cost does not
-    depend on the correlation length (`EnergyEngine.structure_factor`)."""
+    depend on the correlation length (`EnergyEngine.structure_factor`).  Two-site operators, (m, 4, 4) or one (4, 4) matrix with
+    index 2 s1 + s2, pass through: S is then the structure factor of bond operators such as the energy density."""
     eng, K = _resident_states(params, D, state_tensor)
     S, one = eng.structure_factor(ops, k, B=K, want_one_site=True)
     return S, one, eng.results_status(K)
+
+
+def energy_variance(params, H, D=2, state_tensor=ShallowCNOTStateTensor):
+    """Energy variance per site of the states of K parameter rows - the companion of `ground_state_sweep` (params = out['params']):
+      var (K, n_terms)   lim (<H_t^2> - <H_t>^2) / N for H_t = sum_n h_t(n, n+1), per term h_t of H: zero exactly on eigenstates
+      status (K,)        of the environment solve (STATUS_OK = 0; the variance of any other row is not to be trusted)
+    H: a `Hamiltonian`, one (4, 4) matrix or (n_terms, 4, 4) matrices (the variance of a sum of terms needs their cross terms: pass the
+    sum as one matrix).  The variance falls with the bond dimension where the energy alone only says "lower"; it is the natural stopping
+    and extrapolation variable of a sweep over D (`EnergyEngine.energy_variance`)."""
+    h = H.to_matrix() if hasattr(H, 'to_matrix') else np.asarray(H, dtype=np.complex128)
+    eng, K = _resident_states(params, D, state_tensor)
+    return eng.energy_variance(h, B=K), eng.results_status(K)
