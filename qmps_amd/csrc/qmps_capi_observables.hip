@@ -1,5 +1,5 @@
 // qmps_capi_observables.hip - C-ABI of the observables of the resident states: two-point functions (kernels: qmps_correlator.hip),
-// Schmidt spectra and entropies (qmps_entanglement.hip), correlator sums of one-site and of two-site operators (qmps_corrsum.hip).  Every call checks its own arguments,
+// Schmidt spectra and entropies (qmps_entanglement.hip), correlator sums of one-site and of two-site operators (qmps_corrsum.hip and the kernel files it dispatches to).  Every call checks its own arguments,
 // passes the shared front, carves its regions out of the scratch buffer, uploads its inputs, launches ONE kernel, reads its results
 // back and synchronises ONE time.  A refused call writes nothing and allocates nothing.
 #include "qmps_ctx.h"
@@ -77,9 +77,10 @@ int correlator_sums_call(qmps_ctx* c, int64_t B, int n_ops, const double* ops, i
   if (empty) return QMPS_OK;
   if (int rc = ensure_tensors(c)) return rc;
   const int64_t slabs = qmps::correlator_sums_slabs(c->D, B * n_z);
-  const size_t z_bytes = (size_t)n_z * 16, G_bytes = (size_t)B * per_eval, one_bytes = (size_t)B * n_ops * 16, site_bytes = one_bytes * n_ops * (two_site ? 3 : 1);
+  const size_t op_bytes = two_site ? qmps::kTwoSiteOpBytes : qmps::kOneSiteOpBytes, site_values = two_site ? qmps::kTwoSiteSiteValues : qmps::kOneSiteSiteValues;
+  const size_t z_bytes = (size_t)n_z * 16, G_bytes = (size_t)B * per_eval, one_bytes = (size_t)B * n_ops * 16, site_bytes = one_bytes * n_ops * site_values;
   ScratchLayout s;
-  const size_t ops_at = s.take(two_site ? 1024 : 256), z_at = s.take(16384), G_at = s.take(G_bytes), one_at = s.take(one_bytes), site_at = s.take(site_bytes);
+  const size_t ops_at = s.take(qmps::kMaxObservableOps * op_bytes), z_at = s.take(16384), G_at = s.take(G_bytes), one_at = s.take(one_bytes), site_at = s.take(site_bytes);
   // D = 16: the matrices of the workgroups, (G_bytes + one_bytes + site_bytes + 255) / 256 * 256 bytes behind G (the operators and z
   // take multiples of 256 bytes, so rounding the offset is rounding that sum)
   s.align(256);
@@ -87,7 +88,7 @@ int correlator_sums_call(qmps_ctx* c, int64_t B, int n_ops, const double* ops, i
   if (int rc = ensure_scratch(c, s.bytes)) return rc;
   char* base = (char*)c->d_scratch;
   char *d_ops = base + ops_at, *d_z = base + z_at, *d_G = base + G_at, *d_one = base + one_at, *d_site = base + site_at;
-  HIP_TRY(hipMemcpyAsync(d_ops, ops, (size_t)n_ops * (two_site ? 256 : 64), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_ops, ops, (size_t)n_ops * op_bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_z, z, z_bytes, hipMemcpyHostToDevice, c->stream));
   qmps::CorrSumArgs a{};
   a.A = win_A(c);
@@ -130,11 +131,11 @@ int qmps_correlators(qmps_ctx* c, int64_t B, int n_ops, const double* ops, int n
   if (int rc = ensure_tensors(c)) return rc;
   const size_t C_bytes = (size_t)B * per_eval, one_bytes = (size_t)B * n_ops * 16;
   ScratchLayout s;
-  const size_t ops_at = s.take(256), C_at = s.take(C_bytes), one_at = s.take(one_bytes);
+  const size_t ops_at = s.take(qmps::kMaxObservableOps * qmps::kOneSiteOpBytes), C_at = s.take(C_bytes), one_at = s.take(one_bytes);
   if (int rc = ensure_scratch(c, s.bytes)) return rc;
   char* base = (char*)c->d_scratch;
   char *d_ops = base + ops_at, *d_C = base + C_at, *d_one = base + one_at;
-  HIP_TRY(hipMemcpyAsync(d_ops, ops, (size_t)n_ops * 64, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_ops, ops, (size_t)n_ops * qmps::kOneSiteOpBytes, hipMemcpyHostToDevice, c->stream));
   qmps::CorrelatorArgs a{};
   a.A = win_A(c);
   a.r = win_r(c);

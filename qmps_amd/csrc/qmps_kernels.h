@@ -444,6 +444,10 @@ hipError_t launch_stage_copy2(const void* src1, void* dst1, int64_t n1, const vo
 // operators per call of qmps_correlators / qmps_correlator_sums: four span the one-site operators.  The host refuses more, the kernels
 // size their LDS tiles and registers by it
 constexpr int kMaxObservableOps = 4;
+// one operator as the host uploads it and the kernels index it: 2 x 2 complex on one site, 4 x 4 on two; and the values `site` takes
+// per operator pair in the correlator sums (<O_a O_c> on one site; the two-site call: near at the distances 0, +1, -1)
+constexpr int kOneSiteOpBytes = 64, kTwoSiteOpBytes = 256;
+constexpr int kOneSiteSiteValues = 1, kTwoSiteSiteValues = 3;
 // two-point functions (qmps_correlator.hip): one launch for all n_ops^2 n_max values of every evaluation
 struct CorrelatorArgs {
   const void* A;       // [B][2][D][D] complex
@@ -464,7 +468,7 @@ struct EntanglementArgs {
   int64_t B;
 };
 hipError_t launch_entanglement(int D, const EntanglementArgs& a, hipStream_t st);
-// correlator sums (qmps_corrsum.hip): one dense solve of order D^2 per (evaluation, z), one launch
+// correlator sums (dispatch: qmps_corrsum.hip; kernels: qmps_corrsum_small.hip, qmps_corrsum_block.hip): one dense solve of order D^2 per (evaluation, z), one launch
 struct CorrSumArgs {
   const void* A;       // [B][2][D][D] complex
   const void* r;       // [B][D][D] complex right environments (any normalisation: everything is divided by tr r)
@@ -482,7 +486,7 @@ constexpr int kCorrSumMaxSlabs = 252;                     // 252 slabs of 1040 K
 int64_t correlator_sums_slabs(int D, int64_t items);      // slabs the launch wants for this many (evaluation, z) items: 0 unless D = 16
 size_t correlator_sums_slab_bytes();
 hipError_t launch_correlator_sums(int D, const CorrSumArgs& a, hipStream_t st);
-// the same kernels with the two-site source (qmps_corrsum_two_site.h): G sums n >= 2, `site` takes the distances 0, +1, -1
+// the same kernels with the two-site source (qmps_corrsum_two_site.h; the one-site source: qmps_corrsum_one_site.h): G sums n >= 2, `site` takes the distances 0, +1, -1
 hipError_t launch_correlator_sums_two_site(int D, const CorrSumArgs& a, hipStream_t st);
 
 }  // namespace qmps

@@ -1,5 +1,6 @@
 // qmps_observable.h - device helpers shared by the kernels of the observables of the resident states (qmps_correlator.hip,
-// qmps_corrsum.hip); the operator limit kMaxObservableOps they share with the host is in qmps_kernels.h
+// qmps_corrsum_small.hip, qmps_corrsum_block.hip); the operator limit kMaxObservableOps and the operator sizes they share with the
+// host are in qmps_kernels.h
 #pragma once
 #include "qmps_complex.h"
 

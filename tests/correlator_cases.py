@@ -19,7 +19,7 @@ CLD = np.clongdouble
 
 DS = (2, 4, 8, 16)
 BATCHES = (1, 17, 65, 130)            # lane, quad and workgroup tails: prefixes of the one Haar batch per D
-N_OPS = (1, 3, 4)                     # prefixes of `generic_ops()`
+N_OPS = (1, 2, 3, 4)                  # prefixes of `generic_ops()`
 N_SHORT = (1, 2, 7)                   # chain lengths every batch size is taken at ...
 N_LONG = 64                           # ... the long chain: B = 1 and 17
 N_VERY_LONG = 512                     # D = 2, 4 at B = 17 only

@@ -22,7 +22,7 @@ def _reference(D, ops_name, rows, n_max):
 @pytest.mark.parametrize('D', K.DS)
 def test_kernel_alone_within_the_rounding_bound(engine_factory, D):
     """Haar tensors, environments stored, tensors and environments read back; `correlators` against the long-double reference of
-    those arrays, elementwise within bound(D, n): B in (1, 17, 65, 130) x n_ops in (1, 3, 4) x n_max in (1, 2, 7), n_max = 64 at
+    those arrays, elementwise within bound(D, n): B in (1, 17, 65, 130) x n_ops in (1, 2, 3, 4) x n_max in (1, 2, 7), n_max = 64 at
     B = 1 and 17, n_max = 512 at D = 2, 4 (B = 17); non-Hermitian complex operators."""
     eng, s = RS.haar(engine_factory, D)
     (rows_s, n_s), (rows_l, n_l) = K.reference_plan(D)

@@ -10,7 +10,10 @@ CSRC = os.path.join(ROOT, 'qmps_amd', 'csrc')
 SHARED_HELPERS = ('cmul', 'cmulc', 'cfma', 'cfms', 'cfma_conj', 'cfma_cj', 'cmma16', 'cmma16_3m', 'swz32', 'rx_lanes', 'crecip',
                   # the wave-level steps of the 16 x 16 matrix-core solves (qmps_tile16.h)
                   'tile16_to_a_layout', 'tile16_at', 'tile16_publish', 'tile16_fetch', 'tile16_merge_pair', 'tile16_mix_pairs',
-                  'tile16_split_setup', 'tile16_cold_start', 'tile16_warm_start', 'tile16_power_test')
+                  'tile16_split_setup', 'tile16_cold_start', 'tile16_warm_start', 'tile16_power_test',
+                  # the correlator sums: what every kernel shares (qmps_corrsum_core.h) and the helpers of the two sources
+                  'pivot_size', 'pivot_usable', 'pair_products', 'left_products', 'matrix_entry', 'wave_argmax', 'row16_max', 'row16_sum16',
+                  'op_dot', 'op_prod_dot', 'op2_dot', 'op2_prod_dot', 'cross_add')
 
 
 def sources():
@@ -53,3 +56,15 @@ def test_the_overlap_dispatch_file_holds_no_kernels():
     assert '__global__' not in src['qmps_overlap.hip']
     for f in ('qmps_overlap_block.hip', 'qmps_overlap_d16.hip', 'qmps_overlap_square.hip'):
         assert '__global__' in src[f], f
+
+
+def test_the_correlator_sum_dispatch_file_holds_no_kernels_and_no_kernel_asks_for_the_source():
+    """qmps_corrsum.hip checks the arguments and chooses the kernel family; the source of the right-hand sides is a type the kernels
+    are instantiated with (OneSiteSource, TwoSiteSource), never a value they branch on."""
+    src = sources()
+    assert '__global__' not in src['qmps_corrsum.hip']
+    for f in ('qmps_corrsum_small.hip', 'qmps_corrsum_block.hip'):
+        assert '__global__' in src[f], f
+    for f, text in src.items():
+        for gone in ('Source::one_site', 'Source::two_site', 'if constexpr (SRC'):
+            assert gone not in text, (f, gone)

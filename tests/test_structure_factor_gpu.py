@@ -52,7 +52,7 @@ def _check(G, one, site, ref, rows, m, n_z, D, what):
 def test_kernel_alone_within_the_rounding_bound(engine_factory, D):
     """Haar tensors with the environments the device solved, and the small-gap family fed with set_tensors + set_env_guess; tensors and
     environments read back; G elementwise within bound(b, j) of the long-double reference of those arrays, `one` and `site` within
-    correlator_cases.bound(D, 1).  D <= 8: B in (1, 17, 65, 130) x n_ops in (1, 3, 4) x n_z in (1, 2, 6); D = 16: B in (1, 5),
+    correlator_cases.bound(D, 1).  D <= 8: B in (1, 17, 65, 130) x n_ops in (1, 2, 3, 4) x n_z in (1, 2, 6); D = 16: B in (1, 5),
     n_ops in (1, 4), n_z in (1, 3)."""
     eng, s = _haar(engine_factory, D)
     ref = _haar_reference(D)

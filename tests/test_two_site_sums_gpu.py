@@ -46,14 +46,14 @@ def _check(G, one, near, ref, rows, m, n_z, D, what):
 @pytest.mark.parametrize('D', T2.DS)
 def test_kernel_alone_within_the_rounding_bound(engine_factory, D):
     """Haar tensors and the small-gap family with the oracle's direct-solve environments given by set_env_guess; G elementwise within
-    bound(b, j) of the long-double reference, one and near within bound_near().  D <= 8: B in (1, 17, 65, 130) x n_ops in (1, 4) x n_z
+    bound(b, j) of the long-double reference, one and near within bound_near().  D <= 8: B in (1, 17, 65, 130) x n_ops in (1, 2, 3, 4) x n_z
     in (1, 2, 6); D = 16: B in (1, 5), n_ops in (1, 4), n_z in (1, 3)."""
     eng = _haar(engine_factory, D)
     ref = T2.haar_reference(D)
-    batches, n_zs = (T2.BATCHES, T2.N_Z) if D <= 8 else (T2.D16_BATCHES, T2.D16_N_Z)
+    batches, n_ops, n_zs = (T2.BATCHES, T2.N_OPS, T2.N_Z) if D <= 8 else (T2.D16_BATCHES, T2.D16_N_OPS, T2.D16_N_Z)
     worst, worst_near = 0.0, 0.0
     for B in batches:
-        for m in T2.N_OPS:
+        for m in n_ops:
             for n_z in n_zs:
                 G, one, near = eng.correlator_sums(T2.generic_ops()[:m], T2.Z[:n_z], B=B, want_one_site=True, want_site=True)
                 assert G.shape == (B, n_z, m, m) and one.shape == (B, m) and near.shape == (B, m, m, 3) and G.dtype == np.complex128

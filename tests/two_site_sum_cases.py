@@ -40,8 +40,8 @@ LD, CLD, EPS = S.LD, S.CLD, S.EPS
 DS = S.DS
 Z = S.Z
 N_Z, BATCHES = S.N_Z, S.BATCHES
-N_OPS = (1, 4)
-D16_BATCHES, D16_N_Z = S.D16_BATCHES, S.D16_N_Z
+N_OPS = (1, 2, 3, 4)                  # D <= 8: n_ops is a compile-time value of the D = 2 and D = 4 kernels
+D16_BATCHES, D16_N_Z, D16_N_OPS = S.D16_BATCHES, S.D16_N_Z, S.D16_N_OPS
 THETAS = (0.0, 0.7, np.pi / 2)
 C_G = 5.0
 C_NEAR = 40.0
