@@ -2,7 +2,8 @@
 // (qmps_evolve_bfgs: host loop, or - D = 8, 16, round 5 - the optimiser algebra in kernels on device-resident state with the host
 // enqueueing chains of iterations; lock-step groups), the per-trajectory device-resident optimisers of D = 2, 4
 // (qmps_evolve_bfgs_device), and the versioned option structs in front of them.  The rotosolve time evolution: qmps_capi_roto.hip.
-// The overlap objective and gradient they are built on: qmps_capi_overlap.hip (through qmps_overlap_internal.h); context + helpers:
+// The overlap objective and gradient they are built on, and the kernel route of a call (overlap_route, computed once in
+// evolve_bfgs_group): qmps_capi_overlap.hip (through qmps_overlap_internal.h); context + helpers:
 // qmps_capi.hip, qmps_ctx.h.
 #include "qmps_ctx.h"
 #include "qmps_overlap_internal.h"
@@ -36,6 +37,7 @@ struct BfgsGroup {
 
 // What the shared front derives from a group's call, and what either path leaves for the shared write-back.
 struct BfgsRun {
+  OverlapRoute route;                         // of the call (the device algebra enqueues the gradient kernels itself)
   bool carry, warm, two_sided, adaptive;      // warm: the resident fixed points start the next gradient's solves (set by the first one)
   int ladder_rounds, grad_rounds;
   double grad_tol, tol_min, tol_max, tol_rel;
@@ -93,17 +95,10 @@ int evolve_bfgs_device_algebra(const BfgsGroup& job, BfgsRun& run) {
     dv.fh = q; q += (size_t)n_steps * 2 * T; dv.ph = q; q += (size_t)n_steps * TP; dv.alphas = q; q += NA; dv.cand = q; q += (size_t)T * (G > 0 ? G : 1) * P;
     dv.ctl = (int*)q;
     dv.active = (unsigned char*)(dv.ctl + n_ctl + (n_ctl & 1)); dv.eff = dv.active + ((size_t)T + 7) / 8 * 8; dv.need = dv.eff + ((size_t)T + 7) / 8 * 8;
-    if (!c->d_active) HIP_TRY(hipMalloc((void**)&c->d_active, ((size_t)c->max_batch + 7) / 8 * 8));
+    if ((rc = ensure_mask_buffers(c))) return rc;
     if (!c->h_ctl) HIP_TRY(hipHostMalloc((void**)&c->h_ctl, 4096, hipHostMallocDefault));
-    if ((rc = ensure_overlap_outputs(c))) return rc;
-    if (!c->d_y) HIP_TRY(hipMalloc(&c->d_y, (size_t)c->max_batch * env_bytes(c)));
-    { const size_t nD = (size_t)c->D * c->D; if ((rc = ensure_scratch(c, (size_t)T * (4 * nD + 1) * 16 + 256))) return rc; }
+    if ((rc = ensure_gradient_buffers(c, T))) return rc;
     if ((rc = ensure_refs(c, T))) return rc;
-    if (!c->aux_stream) {
-      HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
-    }
     const std::vector<double> tol0(adaptive ? T : 0, run.tol_min);      // (first evaluation: the tightest)
     HIP_TRY(hipMemcpyAsync(dv.X, run.X.data(), TP * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(dv.H, run.Hinv.data(), TP * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -119,7 +114,7 @@ int evolve_bfgs_device_algebra(const BfgsGroup& job, BfgsRun& run) {
     forget_resident_state(c);
     c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0; c->tensors_valid = false; c->n_states = 0;
   }
-  const bool beside = neighbour_build(c, T, kind, P) == NeighbourBuild::Beside;
+  const bool beside = neighbour_build(c, run.route, T, kind, P) == NeighbourBuild::Beside;
   auto lock_args = [&](int step, bool reset_h, int mode) {
     qmps::LockstepArgs la;
     memset(&la, 0, sizeof(la));
@@ -156,9 +151,8 @@ int evolve_bfgs_device_algebra(const BfgsGroup& job, BfgsRun& run) {
     if (beside) HIP_TRY(hipEventRecord(c->aux_fork, c->stream));      // (the second stream builds the neighbours' tensors)
     KernelTimer timer(c, per_eval);
     HIP_TRY(timer.start());
-    c->dominant = c->D == 16 ? "overlap_mfma_d16_kernel + adjoint + neighbour probes" : "overlap solve + adjoint + neighbour probes";
     GradPass gp;
-    if (int e = enqueue_gradient_kernels(c, T, kind, P, d_src, h, run.grad_rounds, run.grad_tol, warm, true, mask, false, gp, adaptive ? dv.tolarr : nullptr)) return e;
+    if (int e = enqueue_gradient_kernels(c, run.route, T, kind, P, d_src, h, run.grad_rounds, run.grad_tol, warm, true, mask, false, gp, adaptive ? dv.tolarr : nullptr)) return e;
     HIP_TRY(timer.stop());
     c->launches++;
     warm = true;
@@ -560,6 +554,7 @@ int evolve_bfgs_group(const BfgsGroup& job) {
   qmps_ctx* c = job.c;
   if (int rc = bind(c)) return rc;
   DisarmOneShots disarm{c};      // nothing armed by this driver outlives it, whichever way it ends
+  const OverlapRoute route = overlap_route(c);
   if (!job.params || !job.WW || !job.f_hist || !job.alphas) return fail(QMPS_ERR_ARG, "null argument");
   const int flags = job.flags, max_rounds = job.max_rounds;
   const double tol = job.tol;
@@ -577,8 +572,7 @@ int evolve_bfgs_group(const BfgsGroup& job) {
   const bool warm = (flags & QMPS_BFGS_WARM) != 0;
   const bool two_sided = c->D >= 4;       // D = 2: the 2 P + 1 central-difference candidates are eigen-solved themselves (a lane each)
   if (warm && two_sided && c->grad_warm_T != T) return fail(QMPS_ERR_STATE, "QMPS_BFGS_WARM: the resident fixed points belong to %lld trajectories, not %lld", (long long)c->grad_warm_T, (long long)T);
-  const bool squaring = overlap_squares(c);
-  const int ladder_rounds = squaring ? (max_rounds > 60 ? 60 : max_rounds) : max_rounds;
+  const int ladder_rounds = route.squares ? (max_rounds > 60 ? 60 : max_rounds) : max_rounds;
   const int grad_rounds = max_rounds > 100000 ? max_rounds : 100000;       // (as _GroupedObjective.value_and_grad)
   // objective by the two-sided quotient (error ~ residual^2): the gradient batches' solves stop at 1e-8 (see qmps_hip.h)
   double grad_tol = (flags & QMPS_BFGS_TIGHT_GRADIENT) ? tol : (tol > 1e-8 ? tol : 1e-8);
@@ -590,7 +584,7 @@ int evolve_bfgs_group(const BfgsGroup& job) {
   const bool adaptive = (flags & QMPS_BFGS_ADAPTIVE_GRADIENT) != 0 && (flags & QMPS_BFGS_TIGHT_GRADIENT) == 0 && two_sided && (c->D == 8 || c->D == 16);
   const double tol_min = grad_tol, tol_max = grad_tol > 1e-6 ? grad_tol : 1e-6, tol_rel = 1e-3;
   const size_t TP = (size_t)T * P;
-  BfgsRun run{carry, warm, two_sided, adaptive, ladder_rounds, grad_rounds, grad_tol, tol_min, tol_max, tol_rel, G, TP,
+  BfgsRun run{route, carry, warm, two_sided, adaptive, ladder_rounds, grad_rounds, grad_tol, tol_min, tol_max, tol_rel, G, TP,
               std::vector<double>(job.params, job.params + TP), std::vector<double>(TP * P)};
   // (a pair of event records around a batch costs the stream ~12 us: only when asked for; restored on EVERY way out of this function)
   Restore<int> period_guard(c->timing_period, job.counters_out ? 1 : 0);
@@ -598,8 +592,9 @@ int evolve_bfgs_group(const BfgsGroup& job) {
   if (carry && warm && job.hinv) memcpy(run.Hinv.data(), job.hinv, TP * P * sizeof(double));
   else for (int64_t t = 0; t < T; ++t) set_identity(run.Hinv, t, P);
   // D = 8, 16: the algebra between two evaluations in kernels; QMPS_EVOLVE_HOST_ALGEBRA selects the host loop for everything
+  // (kept, not meant: at D = 8 the two D16 switches select the host loop as well)
   const bool dev_algebra = two_sided && (c->D == 8 || c->D == 16) && P <= 32 && T <= 65535 && job.maxiter <= 480 && documented_switch("QMPS_EVOLVE_HOST_ALGEBRA") == nullptr &&
-                           documented_switch("QMPS_D16_BLOCK") == nullptr && documented_switch("QMPS_D16_ONE_WAVE") == nullptr;
+                           route.d16_switches_off;
   if (int rc = dev_algebra ? evolve_bfgs_device_algebra(job, run) : evolve_bfgs_host_loop(job, run)) return rc;
   memcpy(job.params, run.X.data(), TP * sizeof(double));
   if (job.hinv) memcpy(job.hinv, run.Hinv.data(), TP * P * sizeof(double));

@@ -1,5 +1,6 @@
 // qmps_capi_overlap.hip - the C-ABI of the time-evolution overlap objective (declared in include/qmps_hip.h): resident references and
-// candidates, the batched objective (resident, or one-shot: qmps_overlap_batch) and its two-sided gradient.  The drivers built on
+// candidates, the batched objective (resident, or one-shot: qmps_overlap_batch) and its two-sided gradient (qmps_overlap_gradient: a
+// list of stages round enqueue_gradient_kernels).  Which kernels they run: overlap_route, once per call.  The drivers built on
 // them: qmps_capi_evolve.hip (BFGS), qmps_capi_roto.hip (rotosolve).  The state setters and the context: qmps_capi.hip; shared
 // helpers: qmps_ctx.h, qmps_overlap_internal.h.
 #include "qmps_ctx.h"
@@ -40,10 +41,49 @@ int ensure_overlap_outputs(qmps_ctx* c) {
   if (c->D >= 8 && !c->d_kry) HIP_TRY(hipMalloc(&c->d_kry, (size_t)c->max_batch * env_bytes(c)));
   return QMPS_OK;
 }
+// the second stream, the left fixed points and the G / probe scratch of a gradient evaluation of T iterates
+int ensure_gradient_buffers(qmps_ctx* c, int64_t T) {
+  if (int rc = ensure_overlap_outputs(c)) return rc;
+  if (!c->d_y) HIP_TRY(hipMalloc(&c->d_y, (size_t)c->max_batch * env_bytes(c)));
+  const size_t nD = (size_t)c->D * c->D;
+  if (int rc = ensure_scratch(c, (size_t)T * (4 * nD + 1) * 16 + 256)) return rc;
+  if (!c->aux_stream) {
+    HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
+  }
+  return QMPS_OK;
+}
+// the device mask (copied in whole 8-byte words) and its pinned staging: two upload slots and the fall-back's (qmps_ctx::kMaskSlot each)
+int ensure_mask_buffers(qmps_ctx* c) {
+  if (!c->d_active) HIP_TRY(hipMalloc((void**)&c->d_active, ((size_t)c->max_batch + 7) / 8 * 8));
+  if (!c->h_mask) HIP_TRY(hipHostMalloc((void**)&c->h_mask, 3 * qmps_ctx::kMaskSlot, hipHostMallocDefault));
+  return QMPS_OK;
+}
+
+// The documented switches are read on every launch: the tests flip them between the launches of one context.
+OverlapRoute overlap_route(const qmps_ctx* c) {
+  const bool d16_block = documented_switch("QMPS_D16_BLOCK") != nullptr, d16_one_wave = documented_switch("QMPS_D16_ONE_WAVE") != nullptr;
+  OverlapRoute r;
+  r.family = c->D == 2 ? OverlapFamily::LaneD2 : (c->D == 4 && !documented_switch("QMPS_OVERLAP_POWER")) ? OverlapFamily::SquareD4 :
+             (c->D == 16 && !d16_block) ? OverlapFamily::MfmaD16 : OverlapFamily::Block;
+  r.squares = r.family == OverlapFamily::LaneD2 || r.family == OverlapFamily::SquareD4;
+  r.mfma = c->D == 4 ? r.squares : !d16_block;
+  r.d16_switches_off = !d16_block && !d16_one_wave;
+  r.split_d16 = c->D == 16 && r.d16_switches_off;
+  r.pair = c->D == 8 || r.split_d16;
+  // (kept, not meant: at D = 8 the two D16 switches turn the fall-back off as well)
+  r.krylov = c->D >= 8 && documented_switch("QMPS_NO_KRYLOV") == nullptr && r.d16_switches_off;
+  r.no_deflation = documented_switch("QMPS_NO_DEFLATION") != nullptr ? 1 : 0;
+  r.name = r.family == OverlapFamily::LaneD2 ? "overlap_lane_kernel" : r.family == OverlapFamily::SquareD4 ? "overlap_square_d4_kernel" :
+           r.family == OverlapFamily::MfmaD16 ? "overlap_mfma_d16_kernel" : "overlap_block_kernel<D>";
+  return r;
+}
+
 // D = 16 batches above 2 048 evaluations: the four-waves-per-evaluation kernel with a work queue (zeroed here, on the stream)
-int arm_queue(qmps_ctx* c, qmps::OverlapArgs& a, int which) {
+int arm_queue(qmps_ctx* c, const OverlapRoute& route, qmps::OverlapArgs& a, int which) {
   a.queue = nullptr;
-  if (c->D != 16 || a.B <= 2048 || documented_switch("QMPS_D16_ONE_WAVE") != nullptr || documented_switch("QMPS_D16_BLOCK") != nullptr) return QMPS_OK;
+  if (!route.split_d16 || a.B <= 2048) return QMPS_OK;
   if (!c->d_queue) return fail(QMPS_ERR_STATE, "overlap work counters not allocated (ensure_overlap_outputs)");
   a.queue = c->d_queue + qmps_ctx::kOverlapQueue + which;
   HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(int), c->stream));
@@ -51,10 +91,10 @@ int arm_queue(qmps_ctx* c, qmps::OverlapArgs& a, int which) {
 }
 // D = 8, 16: arm the Krylov fall-back of a power launch (include/qmps_hip.h "fixed-point solvers"): the power kernel hands a
 // candidate over once its residual history predicts more than krylov_after() further steps.  QMPS_NO_KRYLOV: plain power method.
-int arm_krylov(qmps_ctx* c, qmps::OverlapArgs& a, int which) {
+int arm_krylov(qmps_ctx* c, const OverlapRoute& route, qmps::OverlapArgs& a, int which) {
   a.krylov_after = 0;
   a.kry_counter = nullptr;
-  if (c->D < 8 || documented_switch("QMPS_NO_KRYLOV") != nullptr || documented_switch("QMPS_D16_ONE_WAVE") != nullptr || documented_switch("QMPS_D16_BLOCK") != nullptr) return QMPS_OK;
+  if (!route.krylov) return QMPS_OK;
   if (!c->d_queue || !c->d_kry) return fail(QMPS_ERR_STATE, "Krylov fall-back buffers not allocated (ensure_overlap_outputs)");
   const int after = krylov_after();
   if (after <= 0) return QMPS_OK;
@@ -64,20 +104,17 @@ int arm_krylov(qmps_ctx* c, qmps::OverlapArgs& a, int which) {
   return QMPS_OK;
 }
 
-// the kernel the overlap launch of this context runs (name for qmps_kernel_time) and whether it counts squarings
-bool overlap_squares(const qmps_ctx* c) { return c->D == 2 || (c->D == 4 && !documented_switch("QMPS_OVERLAP_POWER")); }
-int launch_overlap_kernels(qmps_ctx* c, const qmps::OverlapArgs& a_in) {
+// one plain launch of the route's kernel (its name for qmps_kernel_time)
+int launch_overlap_kernels(qmps_ctx* c, const OverlapRoute& route, const qmps::OverlapArgs& a_in) {
   qmps::OverlapArgs a = a_in;
-  if (int rc = arm_queue(c, a, 0)) return rc;
-  if (int rc = arm_krylov(c, a, 0)) return rc;
-  const bool squaring = overlap_squares(c);
-  c->dominant = c->D == 2 ? "overlap_lane_kernel" : (c->D == 4 && squaring ? "overlap_square_d4_kernel" :
-                (c->D == 16 && !documented_switch("QMPS_D16_BLOCK") ? "overlap_mfma_d16_kernel" : "overlap_block_kernel<D>"));
+  if (int rc = arm_queue(c, route, a, 0)) return rc;
+  if (int rc = arm_krylov(c, route, a, 0)) return rc;
+  c->dominant = route.name;
   KernelTimer timer(c, periodic_timing(c));
   HIP_TRY(timer.start());
-  a.no_deflation = documented_switch("QMPS_NO_DEFLATION") != nullptr ? 1 : 0;
-  if (c->D == 2) HIP_TRY(qmps::launch_overlap(a, c->stream));
-  else HIP_TRY(qmps::launch_overlap_d(c->D, a, c->D == 4 ? squaring : documented_switch("QMPS_D16_BLOCK") == nullptr, c->stream));
+  a.no_deflation = route.no_deflation;
+  if (route.family == OverlapFamily::LaneD2) HIP_TRY(qmps::launch_overlap(a, c->stream));
+  else HIP_TRY(qmps::launch_overlap_d(c->D, a, route.mfma, c->stream));
   HIP_TRY(timer.stop());
   if (!c->capturing) c->launches++;
   return QMPS_OK;
@@ -160,11 +197,10 @@ int qmps_overlap_set_active(qmps_ctx* c, int64_t n, const unsigned char* active)
     c->mask_host = nullptr;
     return QMPS_OK;
   }
-  if (!c->d_active) HIP_TRY(hipMalloc((void**)&c->d_active, ((size_t)c->max_batch + 7) / 8 * 8));      // (copied in whole 8-byte words)
   // through pinned staging of its own (the parameter / result regions of h_pin are sized by the drivers and may grow or move), two
   // slots of 512 KiB used alternately: the copy kernel of the previous mask may still be in flight when the host writes the next one
   if ((size_t)n + 8 > qmps_ctx::kMaskSlot) return fail(QMPS_ERR_ARG, "mask longer than 2^19 - 8 entries");
-  if (!c->h_mask) HIP_TRY(hipHostMalloc((void**)&c->h_mask, 3 * qmps_ctx::kMaskSlot, hipHostMallocDefault));
+  if (int rc = ensure_mask_buffers(c)) return rc;
   unsigned char* stage = c->h_mask + (size_t)(c->active_stage ^= 1) * qmps_ctx::kMaskSlot;
   if (c->active_inflight[c->active_stage]) HIP_TRY(hipEventSynchronize(c->active_ev[c->active_stage]));
   memcpy(stage, active, (size_t)n);
@@ -188,9 +224,51 @@ int qmps_overlap_set_active(qmps_ctx* c, int64_t n, const unsigned char* active)
 }
 QMPS_API_CATCH
 
+namespace {
+// the references reach to the end of the window [window, window + B): one for all, one per candidate, or one per candidate group
+int check_reference_cover(const qmps_ctx* c, int64_t B) {
+  const int64_t group = c->overlap_group, end = c->window + B;
+  if (group > 0) {
+    if (c->overlap_refs * group < end) return fail(QMPS_ERR_STATE, "%lld reference tensors x group %lld for window end %lld", (long long)c->overlap_refs, (long long)group, (long long)end);
+  } else if (c->overlap_refs != 1 && c->overlap_refs < end) {
+    return fail(QMPS_ERR_STATE, "%lld reference tensors for window end %lld", (long long)c->overlap_refs, (long long)end);
+  }
+  return QMPS_OK;
+}
+int check_group_alignment(const qmps_ctx* c) {
+  if (c->overlap_group > 0 && c->window % c->overlap_group) return fail(QMPS_ERR_ARG, "with a candidate group the window must start at a multiple of it");
+  return QMPS_OK;
+}
+// the reference of the window's first candidate, and whether all candidates share ONE reference
+// (the window displaces the candidates; with a group the references are addressed by the candidate's GLOBAL index)
+const void* reference_base(const qmps_ctx* c, bool& shared) {
+  const int64_t group = c->overlap_group;
+  shared = group == 0 && c->overlap_refs == 1;
+  return (char*)c->d_ref + (shared ? 0 : (size_t)(group > 0 ? c->window / group : c->window) * tensor_bytes(c));
+}
+// read-backs: an overlap launch has covered the window since the candidates were set
+int check_overlap_results(const qmps_ctx* c, int64_t B) {
+  if (B > 0 && !c->overlap_vals.covers(c->window, c->window + B))
+    return fail(QMPS_ERR_STATE, "no overlap results resident for the window [%lld, %lld): no qmps_overlap_launch has covered it since the candidates were set", (long long)c->window, (long long)(c->window + B));
+  return QMPS_OK;
+}
+// the one-shot mask of qmps_overlap_set_active, one entry per trajectory and `end` of them needed: null, or trajectory `first`'s entry on the device
+int take_mask(qmps_ctx* c, int64_t first, int64_t end, const unsigned char** mask) {
+  *mask = nullptr;
+  if (int e = flush_mask(c)) return e;
+  if (c->active_n > 0) {
+    if (c->active_n < end) return fail(QMPS_ERR_STATE, "qmps_overlap_set_active: %lld entries for %lld trajectories", (long long)c->active_n, (long long)end);
+    *mask = c->d_active + first;
+    c->active_n = 0;
+  }
+  return QMPS_OK;
+}
+}  // namespace
+
 int qmps_overlap_launch(qmps_ctx* c, int64_t B, int max_rounds, double tol, int flags) try {
   if (int rc = bind(c)) return rc;
   DisarmOneShots disarm{c};      // the mask of qmps_overlap_set_active is ONE-SHOT: spent on every way out
+  const OverlapRoute route = overlap_route(c);
   if (int rc = check_window(c, B)) return rc;
   if (c->window + B > c->n_states) return fail(QMPS_ERR_STATE, "window [%lld, %lld) but only %lld states are resident", (long long)c->window, (long long)(c->window + B), (long long)c->n_states);
   if (c->overlap_refs < 1) return fail(QMPS_ERR_STATE, "qmps_overlap_set has not been called");
@@ -199,22 +277,15 @@ int qmps_overlap_launch(qmps_ctx* c, int64_t B, int max_rounds, double tol, int 
   if (warm && !want_r) return fail(QMPS_ERR_ARG, "QMPS_OVERLAP_WARM needs QMPS_OVERLAP_WANT_R (the fixed points stay resident for the next launch)");
   if (warm && !c->have_overlap_x) return fail(QMPS_ERR_STATE, "QMPS_OVERLAP_WARM: no resident fixed points (run a launch with QMPS_OVERLAP_WANT_R first)");
   const int64_t group = c->overlap_group;
-  if (group > 0) {
-    if (c->overlap_refs * group < c->window + B) return fail(QMPS_ERR_STATE, "%lld reference tensors x group %lld for window end %lld", (long long)c->overlap_refs, (long long)group, (long long)(c->window + B));
-  } else if (c->overlap_refs != 1 && c->overlap_refs < c->window + B) {
-    return fail(QMPS_ERR_STATE, "%lld reference tensors for window end %lld", (long long)c->overlap_refs, (long long)(c->window + B));
-  }
-  const bool squaring = overlap_squares(c);   // these square the matrix of the map: rounds, not steps
-  const int cap = squaring ? 60 : (1 << 24);
+  if (int rc = check_reference_cover(c, B)) return rc;
+  const int cap = route.squares ? 60 : (1 << 24);      // squarings of the matrix of the map: rounds, not steps
   if (max_rounds < 1 || max_rounds > cap || !(tol > 0.0)) return fail(QMPS_ERR_ARG, "bad max_rounds / tol (D = %d: max_rounds in [1, %d])", c->D, cap);
   if (int rc = ensure_overlap_outputs(c)) return rc;
   qmps::OverlapArgs a;
   memset(&a, 0, sizeof(a));
-  const bool shared = group == 0 && c->overlap_refs == 1;
-  // (the window displaces the candidates; with a group the references are addressed by the candidate's GLOBAL index)
-  a.A = (shared || group > 0) ? (char*)c->d_ref + (group > 0 ? (size_t)(c->window / group) * tensor_bytes(c) : 0)
-                              : (char*)c->d_ref + (size_t)c->window * tensor_bytes(c);
-  if (group > 0 && c->window % group) return fail(QMPS_ERR_ARG, "with a candidate group the window must start at a multiple of it");
+  bool shared;
+  a.A = reference_base(c, shared);
+  if (int rc = check_group_alignment(c)) return rc;
   if (int rc = ensure_tensors(c)) return rc;
   a.Bt = win_A(c);
   a.WW = c->d_ww;
@@ -223,7 +294,7 @@ int qmps_overlap_launch(qmps_ctx* c, int64_t B, int max_rounds, double tol, int 
   a.r_out = want_r ? win_r(c) : nullptr;
   a.x_in = warm ? win_r(c) : nullptr;
   if (c->warm_from_group > 0) {        // the ladder of a lock-step BFGS iteration: every step length starts from its trajectory's fixed point
-    if (!warm && !squaring && c->window == 0 && group == c->warm_from_group && c->grad_warm_T * group >= B) {
+    if (!warm && !route.squares && c->window == 0 && group == c->warm_from_group && c->grad_warm_T * group >= B) {
       a.x_in = c->d_r;
       a.x_in_group = (int)group;
     }
@@ -232,14 +303,9 @@ int qmps_overlap_launch(qmps_ctx* c, int64_t B, int max_rounds, double tol, int 
   a.stats = c->d_ostats;
   a.group = (int)group;
   a.iters = win_iters(c); a.status = win_status(c); a.B = B; a.a_shared = shared ? 1 : 0; a.max_rounds = max_rounds; a.tol = tol;
-  if (int rc = flush_mask(c)) return rc;
-  if (c->active_n > 0) {           // one-shot mask of qmps_overlap_set_active: one entry per trajectory (candidate group)
-    const int64_t need = group > 0 ? (c->window + B + group - 1) / group : c->window + B;
-    if (c->active_n < need) return fail(QMPS_ERR_STATE, "qmps_overlap_set_active: %lld entries for %lld trajectories", (long long)c->active_n, (long long)need);
-    a.active = c->d_active + (group > 0 ? c->window / group : c->window);
-    c->active_n = 0;
-  }
-  if (int rc = launch_overlap_kernels(c, a)) return rc;
+  // (a trajectory is a candidate group)
+  if (int rc = take_mask(c, group > 0 ? c->window / group : c->window, group > 0 ? (c->window + B + group - 1) / group : c->window + B, &a.active)) return rc;
+  if (int rc = launch_overlap_kernels(c, route, a)) return rc;
   forget_environments(c);
   c->counts.remove(c->window, c->window + B);     // the window's iteration counts and statuses are this launch's now
   c->overlap_vals.add(c->window, c->window + B);
@@ -261,8 +327,7 @@ int qmps_overlap_get(qmps_ctx* c, int64_t B, double* eta_out, double* r_out, int
   if (int rc = check_window(c, B)) return rc;
   if (!eta_out) return fail(QMPS_ERR_ARG, "null eta_out");
   if (!c->d_eta) return fail(QMPS_ERR_STATE, "qmps_overlap_launch has not been called");
-  if (B > 0 && !c->overlap_vals.covers(c->window, c->window + B))
-    return fail(QMPS_ERR_STATE, "no overlap results resident for the window [%lld, %lld): no qmps_overlap_launch has covered it since the candidates were set", (long long)c->window, (long long)(c->window + B));
+  if (int rc = check_overlap_results(c, B)) return rc;
   HIP_TRY(hipMemcpyAsync(eta_out, (char*)c->d_eta + (size_t)c->window * 16, (size_t)B * 16, hipMemcpyDeviceToHost, c->stream));
   if (r_out) {
     if (!c->have_overlap_x || (B > 0 && !c->overlap_x.covers(c->window, c->window + B)))
@@ -281,8 +346,7 @@ int qmps_overlap_get_objective(qmps_ctx* c, int64_t B, double* f_out) try {
   if (int rc = check_window(c, B)) return rc;
   if (!f_out) return fail(QMPS_ERR_ARG, "null f_out");
   if (!c->d_f) return fail(QMPS_ERR_STATE, "qmps_overlap_launch has not been called");
-  if (B > 0 && !c->overlap_vals.covers(c->window, c->window + B))
-    return fail(QMPS_ERR_STATE, "no overlap results resident for the window [%lld, %lld): no qmps_overlap_launch has covered it since the candidates were set", (long long)c->window, (long long)(c->window + B));
+  if (int rc = check_overlap_results(c, B)) return rc;
   HIP_TRY(hipMemcpyAsync(f_out, c->d_f + c->window, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return QMPS_OK;
@@ -316,13 +380,8 @@ int qmps_overlap_amplitude(qmps_ctx* c, int64_t B, const double* q, double* amp_
   if (!q || !amp_out) return fail(QMPS_ERR_ARG, "null argument");
   if (c->window + B > c->n_states) return fail(QMPS_ERR_STATE, "window [%lld, %lld) but only %lld states are resident", (long long)c->window, (long long)(c->window + B), (long long)c->n_states);
   if (c->overlap_refs < 1) return fail(QMPS_ERR_STATE, "qmps_overlap_set has not been called");
-  const int64_t group = c->overlap_group;
-  if (group > 0) {
-    if (c->window % group) return fail(QMPS_ERR_ARG, "with a candidate group the window must start at a multiple of it");
-    if (c->overlap_refs * group < c->window + B) return fail(QMPS_ERR_STATE, "%lld reference tensors x group %lld for window end %lld", (long long)c->overlap_refs, (long long)group, (long long)(c->window + B));
-  } else if (c->overlap_refs != 1 && c->overlap_refs < c->window + B) {
-    return fail(QMPS_ERR_STATE, "%lld reference tensors for window end %lld", (long long)c->overlap_refs, (long long)(c->window + B));
-  }
+  if (int rc = check_group_alignment(c)) return rc;
+  if (int rc = check_reference_cover(c, B)) return rc;
   if (int rc = ensure_tensors(c)) return rc;
   // environments in and amplitudes out through the scratch arena: neither the resident fixed points nor eta of a launch are touched
   const size_t qb = (size_t)B * env_bytes(c), ob = (size_t)B * 16;
@@ -330,14 +389,13 @@ int qmps_overlap_amplitude(qmps_ctx* c, int64_t B, const double* q, double* amp_
   HIP_TRY(hipMemcpyAsync(c->d_scratch, q, qb, hipMemcpyHostToDevice, c->stream));
   qmps::OverlapArgs a;
   memset(&a, 0, sizeof(a));
-  const bool shared = group == 0 && c->overlap_refs == 1;
-  a.A = (shared || group > 0) ? (char*)c->d_ref + (group > 0 ? (size_t)(c->window / group) * tensor_bytes(c) : 0)
-                              : (char*)c->d_ref + (size_t)c->window * tensor_bytes(c);
+  bool shared;
+  a.A = reference_base(c, shared);
   a.Bt = win_A(c);
   a.WW = c->d_ww;
   a.x_in = c->d_scratch;
   a.eta = (char*)c->d_scratch + qb;
-  a.B = B; a.a_shared = shared ? 1 : 0; a.group = (int)group;
+  a.B = B; a.a_shared = shared ? 1 : 0; a.group = (int)c->overlap_group;
   HIP_TRY(qmps::launch_overlap_amplitude(c->D, a, c->stream));
   HIP_TRY(hipMemcpyAsync(amp_out, a.eta, ob, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -410,11 +468,10 @@ int qmps_overlap_eval_ansatz(qmps_ctx* c, int64_t B, int kind, int n_params, con
 QMPS_API_CATCH
 
 namespace qmps_host {
-NeighbourBuild neighbour_build(const qmps_ctx* c, int64_t T, int kind, int P) {
+NeighbourBuild neighbour_build(const qmps_ctx* c, const OverlapRoute& route, int64_t T, int kind, int P) {
   // D = 16, ShallowCNOT families: by the surplus workgroups of the pair launch (round 5; not with the kernels of QMPS_D16_BLOCK and
   // QMPS_D16_ONE_WAVE) - no second stream and none of its two cross-stream dependencies (~7 us each per evaluation)
-  if (qmps::neighbour_build_in_pair(c->D, kind, P) && documented_switch("QMPS_D16_BLOCK") == nullptr && documented_switch("QMPS_D16_ONE_WAVE") == nullptr)
-    return NeighbourBuild::InPair;
+  if (route.split_d16 && qmps::neighbour_build_in_pair(c->D, kind, P)) return NeighbourBuild::InPair;
   // otherwise on a second stream BESIDE the eigen-solves: they need the parameters only (at small T a gradient batch is the latency
   // of its slowest solve; the neighbour tensors were a fifth of it in front of the probes)
   // (beyond ~1 000 iterates the solves fill the chip by themselves: T = 2 048 measured 5 % slower with the second stream)
@@ -422,7 +479,50 @@ NeighbourBuild neighbour_build(const qmps_ctx* c, int64_t T, int kind, int P) {
   // land on the same hardware queue serialise - measured 5-10 % slower and erratic, profiles/EXPERIMENTS.md round 4)
   return T <= 1024 && !c->one_stream ? NeighbourBuild::Beside : NeighbourBuild::Inline;
 }
+}  // namespace qmps_host
 
+namespace {
+// ---- the four ways of getting the right (gp.a) and the left (gp.l) fixed points of a gradient evaluation ------------------------
+// The Krylov fall-back of the two solves of a pair launch.  Lazy: launched only if a status asks for it (krylov_second_pass) -
+// behind every batch, it cost a warm batch of 256 iterates - which never hands anything over - an empty launch and a launch gap,
+// ~10 us of ~200.
+int arm_krylov_pair(qmps_ctx* c, const OverlapRoute& route, bool allow_lazy_krylov, GradPass& gp) {
+  if (int e = arm_krylov(c, route, gp.a, 0)) return e;
+  if (int e = arm_krylov(c, route, gp.l, 1)) return e;
+  gp.lazy_krylov = allow_lazy_krylov && gp.a.krylov_after > 0 && gp.l.krylov_after > 0 && gp.a.kry_counter != nullptr && gp.l.kry_counter != nullptr;
+  return QMPS_OK;
+}
+// D = 16: both solves in ONE launch - the iteration chains are latency-bound, so the left solve rides along (more than 2 048
+// iterates: the workgroups draw them from two queues) - and the central-difference neighbours' tensors by the surplus workgroups
+// of the same launch (nb; null: built elsewhere)
+int solve_pair_d16(qmps_ctx* c, const OverlapRoute& route, bool allow_lazy_krylov, const qmps::NeighbourBuildArgs* nb, GradPass& gp) {
+  if (int e = arm_queue(c, route, gp.a, 0)) return e;
+  if (int e = arm_queue(c, route, gp.l, 1)) return e;
+  if (int e = arm_krylov_pair(c, route, allow_lazy_krylov, gp)) return e;
+  HIP_TRY(qmps::launch_overlap_pair_d16(gp.a, gp.l, c->stream, !gp.lazy_krylov, nb));
+  return QMPS_OK;
+}
+// D = 8: the same - one launch, the left solves on the SIMDs the right ones leave idle
+int solve_pair_d8(qmps_ctx* c, const OverlapRoute& route, bool allow_lazy_krylov, GradPass& gp) {
+  if (int e = arm_krylov_pair(c, route, allow_lazy_krylov, gp)) return e;
+  HIP_TRY(qmps::launch_overlap_pair_d8(gp.a, gp.l, c->stream, !gp.lazy_krylov));
+  return QMPS_OK;
+}
+// D = 4: largest column AND largest row of the squared map in one launch (right and left fixed point, whatever the gap)
+int solve_square_d4(qmps_ctx* c, GradPass& gp) {
+  gp.a.l_out = c->d_y;
+  HIP_TRY(qmps::launch_overlap_d(c->D, gp.a, true, c->stream));
+  return QMPS_OK;
+}
+// two launches of their own: the block kernel (D = 4 under QMPS_OVERLAP_POWER, D = 16 under QMPS_D16_BLOCK), D = 16 under QMPS_D16_ONE_WAVE
+int solve_separately(qmps_ctx* c, const OverlapRoute& route, GradPass& gp) {
+  HIP_TRY(qmps::launch_overlap_d(c->D, gp.a, route.mfma, c->stream));
+  HIP_TRY(qmps::launch_overlap_d(c->D, gp.l, route.mfma, c->stream));
+  return QMPS_OK;
+}
+}  // namespace
+
+namespace qmps_host {
 // One gradient evaluation of T iterates, ENQUEUED on the context stream and nothing else: [right + left fixed points] beside [the
 // 2 P central-difference neighbours' tensors], then [G + probes].  The iterates' tensors are in d_A[0, T), their parameter rows at
 // d_src (device).  Where the neighbour tensors are built: neighbour_build; NeighbourBuild::Beside waits for c->aux_fork on the
@@ -432,197 +532,137 @@ NeighbourBuild neighbour_build(const qmps_ctx* c, int64_t T, int kind, int P) {
 // Outputs: d_f[0, T) objective of the iterates, d_f[T, T + 2 P T) of the neighbours, d_status[0, T) / [T, 2 T) right / left solves,
 // d_r / d_y the fixed points (the next call's warm start).  Shared by qmps_overlap_gradient (host loop) and the device-resident
 // lock-step BFGS of qmps_evolve_bfgs.
-int enqueue_gradient_kernels(qmps_ctx* c, int64_t T, int kind, int P, const double* d_src, double h, int max_rounds, double tol, bool warm, bool two_sided_f,
-                             const unsigned char* mask, bool allow_lazy_krylov, GradPass& gp, const double* tol_in) {
-  const bool squaring = overlap_squares(c);       // D = 4: the right fixed point comes from the squaring kernel (largest column)
+int enqueue_gradient_kernels(qmps_ctx* c, const OverlapRoute& route, int64_t T, int kind, int P, const double* d_src, double h, int max_rounds, double tol, bool warm,
+                             bool two_sided_f, const unsigned char* mask, bool allow_lazy_krylov, GradPass& gp, const double* tol_in) {
+  c->dominant = c->D == 16 ? "overlap_mfma_d16_kernel + adjoint + neighbour probes" : "overlap solve + adjoint + neighbour probes";
   qmps::OverlapArgs& a = gp.a;
   memset(&a, 0, sizeof(a));
   a.A = c->d_ref; a.Bt = c->d_A; a.WW = c->d_ww; a.eta = c->d_eta; a.f_out = c->d_f; a.r_out = c->d_r;
-  a.x_in = (warm && !squaring) ? c->d_r : nullptr;
+  a.x_in = (warm && !route.squares) ? c->d_r : nullptr;
   a.stats = c->d_ostats; a.iters = c->d_iters; a.status = c->d_status; a.B = T; a.a_shared = 0;
-  a.max_rounds = squaring && max_rounds > 60 ? 60 : max_rounds; a.tol = tol;
+  a.max_rounds = route.squares && max_rounds > 60 ? 60 : max_rounds; a.tol = tol;
   a.active = mask;
   a.tol_in = (c->D == 8 || c->D == 16) ? tol_in : nullptr;      // per-trajectory tolerances (the lock-step BFGS; the left solve inherits them)
-  // The Krylov fall-back of the two solves is launched only if a status asks for it (below): behind every batch, it cost a warm
-  // batch of 256 iterates - which never hands anything over - an empty launch and a launch gap, ~10 us of ~200.
-  bool lazy_krylov = false;
-  const size_t nD = (size_t)c->D * c->D;
-  const NeighbourBuild nbuild = neighbour_build(c, T, kind, P);
+  a.no_deflation = route.no_deflation;
   // the left fixed points: power method on the adjoint map; results behind the iterates' (eta, rounds, status at [T, 2T))
   qmps::OverlapArgs& l = gp.l;
   l = a;
   l.adjoint = 1; l.eta = (char*)c->d_eta + (size_t)T * 16; l.f_out = nullptr; l.r_out = c->d_y; l.x_in = warm ? c->d_y : nullptr;
   l.iters = c->d_iters + T; l.status = c->d_status + T; l.max_rounds = max_rounds;
-  if (c->D == 16 && documented_switch("QMPS_D16_BLOCK") == nullptr && documented_switch("QMPS_D16_ONE_WAVE") == nullptr) {
-    // both solves in ONE launch: the iteration chains are latency-bound, so the left solve rides along (more than 2 048
-    // iterates: the workgroups draw them from two queues)
-    a.no_deflation = l.no_deflation = documented_switch("QMPS_NO_DEFLATION") != nullptr ? 1 : 0;
-    if (int e = arm_queue(c, a, 0)) return e;
-    if (int e = arm_queue(c, l, 1)) return e;
-    if (int e = arm_krylov(c, a, 0)) return e;
-    if (int e = arm_krylov(c, l, 1)) return e;
-    lazy_krylov = allow_lazy_krylov && a.krylov_after > 0 && l.krylov_after > 0 && a.kry_counter != nullptr && l.kry_counter != nullptr;
-    // ... and the central-difference neighbours' tensors by the surplus workgroups of the same launch (ShallowCNOT families)
-    qmps::NeighbourBuildArgs nb;
-    memset(&nb, 0, sizeof(nb));
-    if (nbuild == NeighbourBuild::InPair) {
-      nb.params = d_src; nb.out = (char*)c->d_A + (size_t)T * tensor_bytes(c); nb.rows = T; nb.n_params = P; nb.kind = kind; nb.h = h; nb.active = mask;
-    }
-    HIP_TRY(qmps::launch_overlap_pair_d16(a, l, c->stream, !lazy_krylov, nbuild == NeighbourBuild::InPair ? &nb : nullptr));
-  } else if (c->D == 8) {
-    // D = 8: the same - one launch, the left solves on the SIMDs the right ones leave idle
-    a.no_deflation = l.no_deflation = documented_switch("QMPS_NO_DEFLATION") != nullptr ? 1 : 0;
-    if (int e = arm_krylov(c, a, 0)) return e;
-    if (int e = arm_krylov(c, l, 1)) return e;
-    lazy_krylov = allow_lazy_krylov && a.krylov_after > 0 && l.krylov_after > 0 && a.kry_counter != nullptr && l.kry_counter != nullptr;
-    HIP_TRY(qmps::launch_overlap_pair_d8(a, l, c->stream, !lazy_krylov));
-  } else if (c->D == 4 && squaring) {
-    // D = 4: largest column AND largest row of the squared map in one launch (right and left fixed point, whatever the gap)
-    a.l_out = c->d_y;
-    HIP_TRY(qmps::launch_overlap_d(c->D, a, true, c->stream));
-  } else {
-    a.no_deflation = documented_switch("QMPS_NO_DEFLATION") != nullptr ? 1 : 0;
-    HIP_TRY(qmps::launch_overlap_d(c->D, a, c->D == 4 ? squaring : documented_switch("QMPS_D16_BLOCK") == nullptr, c->stream));
-    // (D = 4: the squaring kernel again - the left fixed point is the largest row of the squared map, whatever the spectral gap)
-    if (c->D == 4 && squaring) l.max_rounds = a.max_rounds;
-    l.no_deflation = documented_switch("QMPS_NO_DEFLATION") != nullptr ? 1 : 0;
-    HIP_TRY(qmps::launch_overlap_d(c->D, l, c->D == 4 ? squaring : (c->D == 16 && documented_switch("QMPS_D16_BLOCK") == nullptr), c->stream));
+  const NeighbourBuild nbuild = neighbour_build(c, route, T, kind, P);
+  void* const neighbours = (char*)c->d_A + (size_t)T * tensor_bytes(c);
+  qmps::NeighbourBuildArgs nb;
+  memset(&nb, 0, sizeof(nb));
+  if (nbuild == NeighbourBuild::InPair) {
+    nb.params = d_src; nb.out = neighbours; nb.rows = T; nb.n_params = P; nb.kind = kind; nb.h = h; nb.active = mask;
   }
+  int rc;
+  if (route.split_d16) rc = solve_pair_d16(c, route, allow_lazy_krylov, nbuild == NeighbourBuild::InPair ? &nb : nullptr, gp);
+  else if (route.pair) rc = solve_pair_d8(c, route, allow_lazy_krylov, gp);
+  else if (route.family == OverlapFamily::SquareD4) rc = solve_square_d4(c, gp);
+  else rc = solve_separately(c, route, gp);
+  if (rc) return rc;
   if (nbuild == NeighbourBuild::Beside) {
     HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->aux_fork, 0));
-    HIP_TRY(qmps::launch_ansatz_fd(c->D, kind, d_src, P, (char*)c->d_A + (size_t)T * tensor_bytes(c), T, h, c->aux_stream, mask));
+    HIP_TRY(qmps::launch_ansatz_fd(c->D, kind, d_src, P, neighbours, T, h, c->aux_stream, mask));
     HIP_TRY(hipEventRecord(c->aux_join, c->aux_stream));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->aux_join, 0));
   } else if (nbuild == NeighbourBuild::Inline) {
-    HIP_TRY(qmps::launch_ansatz_fd(c->D, kind, d_src, P, (char*)c->d_A + (size_t)T * tensor_bytes(c), T, h, c->stream, mask));
+    HIP_TRY(qmps::launch_ansatz_fd(c->D, kind, d_src, P, neighbours, T, h, c->stream, mask));
   }
+  const size_t nD = (size_t)c->D * c->D;
   qmps::OverlapGradArgs& g = gp.g;
   memset(&g, 0, sizeof(g));
   g.A = c->d_ref; g.WW = c->d_ww; g.r = c->d_r; g.y = c->d_y; g.G = c->d_scratch; g.yr = (char*)c->d_scratch + (size_t)T * 4 * nD * 16;
-  g.Bt = (char*)c->d_A + (size_t)T * tensor_bytes(c); g.f_out = c->d_f + T; g.T = T; g.G2P = 2 * P; g.active = mask;
+  g.Bt = neighbours; g.f_out = c->d_f + T; g.T = T; g.G2P = 2 * P; g.active = mask;
   if (two_sided_f) { g.Bc = c->d_A; g.fc_out = c->d_f; }       // (overwrites the right solve's own estimate)
   HIP_TRY(qmps::launch_overlap_grad(c->D, g, c->stream));
-  gp.lazy_krylov = lazy_krylov;
   return QMPS_OK;
 }
 }  // namespace qmps_host
 
-int qmps_overlap_gradient(qmps_ctx* c, int64_t T, int kind, int n_params, const double* params, double h, int max_rounds, double tol,
-                          int flags, double* f_out, double* g_out, int32_t* status_out) try {
-  if (int rc = bind(c)) return rc;
-  DisarmOneShots disarm{c};      // (one-shot mask: spent on every way out)
-  if (!params || !f_out || !g_out) return fail(QMPS_ERR_ARG, "null argument");
-  if (c->D < 4) return fail(QMPS_ERR_ARG, "qmps_overlap_gradient: D = 4, 8, 16 (at D = 2 evaluate the central-difference neighbours themselves)");
-  if (flags & ~(QMPS_OVERLAP_WARM | QMPS_OVERLAP_TWO_SIDED_F)) return fail(QMPS_ERR_ARG, "unknown flag bits 0x%x", flags);
-  if (!(h > 0.0)) return fail(QMPS_ERR_ARG, "h must be > 0");
-  const int P = n_params;
-  if (T < 1 || T * (1 + 2 * (int64_t)P) > c->max_batch) return fail(QMPS_ERR_ARG, "T (1 + 2 n_params) = %lld evaluations exceed max_batch = %lld", (long long)(T * (1 + 2 * (int64_t)P)), (long long)c->max_batch);
-  if (c->overlap_refs < T) return fail(QMPS_ERR_STATE, "%lld reference tensors resident, %lld trajectories (qmps_overlap_set / qmps_overlap_set_refs_ansatz)", (long long)c->overlap_refs, (long long)T);
-  if (max_rounds < 1 || max_rounds > (1 << 24) || !(tol > 0.0)) return fail(QMPS_ERR_ARG, "bad max_rounds / tol");
-  const bool warm = (flags & QMPS_OVERLAP_WARM) != 0;
-  if (warm && c->grad_warm_T != T) return fail(QMPS_ERR_STATE, "QMPS_OVERLAP_WARM: the resident fixed points belong to %lld trajectories, not %lld", (long long)c->grad_warm_T, (long long)T);
-  if (int rc = ensure_overlap_outputs(c)) return rc;
-  if (!c->d_y) HIP_TRY(hipMalloc(&c->d_y, (size_t)c->max_batch * env_bytes(c)));
-  const size_t nD = (size_t)c->D * c->D;
-  if (int rc = ensure_scratch(c, (size_t)T * (4 * nD + 1) * 16 + 256)) return rc;
-  {      // pinned staging for the results, sized BEFORE anything is in flight through it
-    const size_t need = (size_t)T * (1 + 2 * P) * sizeof(double) + (size_t)2 * T * sizeof(int32_t) + (8u << 20);
-    if (int e = ensure_pinned(c, need > (16u << 20) ? need : (16u << 20))) return e;
-  }
-  // the 2 P central-difference neighbours of every iterate (evaluated below to second order in h from (y, r)): neighbour_build
-  if (!c->aux_stream) {
-    HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
-  }
-  const bool beside = neighbour_build(c, T, kind, P) == NeighbourBuild::Beside;
-  // the iterates: parameters -> tensors in d_A[0, T); the fork event sits between the parameter upload and the tensor build, and
-  // the second stream is fed only AFTER the solves are submitted (the host calls of the fork used to hold the solves back ~15 us)
+namespace {
+// ---- the stages of qmps_overlap_gradient behind the shared enqueue -------------------------------------------------------------
+// Where a batch's results land in the pinned staging: f of the iterates and of their 2 P neighbours (contiguous in d_f: one copy),
+// then the statuses of both solves (one copy)
+struct GradStaging {
+  double* f;
+  int32_t* st;
+  size_t fbytes, sbytes;
+};
+int ensure_staging(qmps_ctx* c, int64_t T, int P, GradStaging& s) {      // sized BEFORE anything is in flight through it
+  s.fbytes = (size_t)T * (1 + 2 * P) * sizeof(double);
+  s.sbytes = (size_t)2 * T * sizeof(int32_t);
+  const size_t need = s.fbytes + s.sbytes + (8u << 20);
+  if (int e = ensure_pinned(c, need > (16u << 20) ? need : (16u << 20))) return e;
+  s.f = (double*)(c->h_pin + (8u << 20));
+  s.st = (int32_t*)(c->h_pin + (8u << 20) + s.fbytes);
+  return QMPS_OK;
+}
+// the iterates: parameters -> tensors in d_A[0, T); the fork event sits between the parameter upload and the tensor build, and
+// the second stream is fed only AFTER the solves are submitted (the host calls of the fork used to hold the solves back ~15 us)
+int upload_iterates(qmps_ctx* c, int64_t T, int kind, int P, const double* params, bool fork) {
   int rc;
   {
     Restore<bool> deferred(c->defer_sync, true);
-    if (beside) c->fork_after_copy = c->aux_fork;
+    if (fork) c->fork_after_copy = c->aux_fork;
     rc = qmps_set_states_ansatz(c, T, kind, P, params);
   }
   if (!rc) rc = ensure_tensors(c);
-  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-  const unsigned char* mask = nullptr;
-  if (int e = flush_mask(c)) return e;
-  if (c->active_n > 0) {
-    if (c->active_n < T) return fail(QMPS_ERR_STATE, "qmps_overlap_set_active: %lld entries for %lld trajectories", (long long)c->active_n, (long long)T);
-    mask = c->d_active;
-    c->active_n = 0;
-  }
-  // HIP events around the WHOLE gradient evaluation (right solve, left solve, neighbour tensors, G, probes): qmps_kernel_time
-  c->dominant = c->D == 16 ? "overlap_mfma_d16_kernel + adjoint + neighbour probes" : "overlap solve + adjoint + neighbour probes";
-  KernelTimer timer(c, periodic_timing(c));
-  HIP_TRY(timer.start());
-  if (beside && c->fork_after_copy) {        // (the parameter upload took another path: it did not record the fork)
-    c->fork_after_copy = nullptr;
-    return fail(QMPS_ERR_STATE, "qmps_overlap_gradient: the parameter upload did not record the fork event");
-  }
-  // The Krylov fall-back of the two solves is launched only if a status asks for it (below): behind every batch, it cost a warm
-  // batch of 256 iterates - which never hands anything over - an empty launch and a launch gap, ~10 us of ~200.
-  GradPass gp;
-  const double* tol_in = c->grad_tol_in;        // one-shot (qmps_evolve_bfgs, host loop): per-trajectory tolerances
-  c->grad_tol_in = nullptr;
-  if (int e = enqueue_gradient_kernels(c, T, kind, P, c->d_params, h, max_rounds, tol, warm, (flags & QMPS_OVERLAP_TWO_SIDED_F) != 0, mask, true, gp, tol_in)) return e;
-  const bool lazy_krylov = gp.lazy_krylov;
-  qmps::OverlapArgs &a = gp.a, &l = gp.l;
-  qmps::OverlapGradArgs& g = gp.g;
-  HIP_TRY(timer.stop());
-  c->launches++;
-  // f of the iterates and of their neighbours are contiguous in d_f: one copy; statuses of both solves: one copy (pinned staging)
-  // (tried: the two kernels writing pinned host mirrors themselves instead of the copy kernel - 4 352 eight-byte writes over the
-  // host link are slower than one coalesced burst: 0.78 - 0.80 -> 0.80 - 0.83 ms per time step at 256 trajectories)
-  const size_t fbytes = (size_t)T * (1 + 2 * P) * sizeof(double), sbytes = (size_t)2 * T * sizeof(int32_t);
-  double* fall = (double*)(c->h_pin + (8u << 20));
-  int32_t* st = (int32_t*)(c->h_pin + (8u << 20) + fbytes);
-  // (tried: a completion flag in pinned memory written by the copy kernel's last block and polled by the host instead of
-  // hipStreamSynchronize - the wait shrinks by 7 us, the next submission grows by 11: no gain)
-  HIP_TRY(qmps::launch_stage_copy2(c->d_f, fall, (int64_t)(fbytes / 8), c->d_status, st, (int64_t)(sbytes / 8), c->stream));
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+// (tried: the two kernels writing pinned host mirrors themselves instead of the copy kernel - 4 352 eight-byte writes over the
+// host link are slower than one coalesced burst: 0.78 - 0.80 -> 0.80 - 0.83 ms per time step at 256 trajectories)
+// (tried: a completion flag in pinned memory written by the copy kernel's last block and polled by the host instead of
+// hipStreamSynchronize - the wait shrinks by 7 us, the next submission grows by 11: no gain)
+int read_back(qmps_ctx* c, const GradStaging& s) {
+  HIP_TRY(qmps::launch_stage_copy2(c->d_f, s.f, (int64_t)(s.fbytes / 8), c->d_status, s.st, (int64_t)(s.sbytes / 8), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (lazy_krylov) {
-    // a solve that stopped short (handed over by the power kernel, or at its cap): the fall-back kernel, then G and the probes of
-    // those trajectories once more (everything else keeps its values), then the read-back again
-    // (skipped trajectories keep the statuses of earlier launches: they do not count)
-    const unsigned char* hm = mask != nullptr ? c->mask_host : nullptr;
-    bool any = false;
-    for (int64_t t = 0; t < T && !any; ++t)
-      any = (mask == nullptr || hm == nullptr || hm[t] != 0) && (st[t] == qmps::QMPS_ST_NOT_CONVERGED || st[T + t] == qmps::QMPS_ST_NOT_CONVERGED);
-    if (any) {
-      if (!c->d_active) HIP_TRY(hipMalloc((void**)&c->d_active, ((size_t)c->max_batch + 7) / 8 * 8));
-      if ((size_t)T + 8 > qmps_ctx::kMaskSlot) return fail(QMPS_ERR_ARG, "qmps_overlap_gradient: fall-back mask for %lld trajectories exceeds the staging slot", (long long)T);
-      if (!c->h_mask) HIP_TRY(hipHostMalloc((void**)&c->h_mask, 3 * qmps_ctx::kMaskSlot, hipHostMallocDefault));
-      unsigned char* fix = c->h_mask + 2 * qmps_ctx::kMaskSlot;           // (third slot: never one of the two upload slots)
-      std::vector<unsigned char> was(T, 1);
-      if (hm != nullptr) was.assign(hm, hm + T);
-      for (int64_t t = 0; t < T; ++t) fix[t] = (was[t] != 0 && (st[t] == qmps::QMPS_ST_NOT_CONVERGED || st[T + t] == qmps::QMPS_ST_NOT_CONVERGED)) ? 1 : 0;
-      for (int64_t t = T; t < (T + 7) / 8 * 8; ++t) fix[t] = 0;
-      HIP_TRY(qmps::launch_overlap_krylov_pair(c->D, a, l, c->stream));
-      HIP_TRY(qmps::launch_stage_copy(fix, c->d_active, (T + 7) / 8, c->stream));
-      g.active = c->d_active;
-      HIP_TRY(qmps::launch_overlap_grad(c->D, g, c->stream));
-      // the timed interval of this batch ends HERE when there was a second pass (Krylov pair, G, probes): kernel time, the evolve
-      // drivers' gradient_ms and kernel_share_of_wall count the fall-back too (the first read-back sits inside the interval: the
-      // cost of discovering the stragglers)
-      HIP_TRY(timer.extend());
-      HIP_TRY(qmps::launch_stage_copy2(c->d_f, fall, (int64_t)(fbytes / 8), c->d_status, st, (int64_t)(sbytes / 8), c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-  }
-  memcpy(f_out, fall, (size_t)T * sizeof(double));
-  const double* fn = fall + T;
+  return QMPS_OK;
+}
+// a solve that stopped short (handed over by the power kernel, or at its cap): the fall-back kernel, then G and the probes of
+// those trajectories once more (everything else keeps its values), then the read-back again
+int krylov_second_pass(qmps_ctx* c, int64_t T, const unsigned char* mask, GradPass& gp, const KernelTimer& timer, const GradStaging& s) {
+  // (skipped trajectories keep the statuses of earlier launches: they do not count)
+  const unsigned char* hm = mask != nullptr ? c->mask_host : nullptr;
+  const int32_t* st = s.st;
+  bool any = false;
+  for (int64_t t = 0; t < T && !any; ++t)
+    any = (mask == nullptr || hm == nullptr || hm[t] != 0) && (st[t] == qmps::QMPS_ST_NOT_CONVERGED || st[T + t] == qmps::QMPS_ST_NOT_CONVERGED);
+  if (!any) return QMPS_OK;
+  if ((size_t)T + 8 > qmps_ctx::kMaskSlot) return fail(QMPS_ERR_ARG, "qmps_overlap_gradient: fall-back mask for %lld trajectories exceeds the staging slot", (long long)T);
+  if (int rc = ensure_mask_buffers(c)) return rc;
+  unsigned char* fix = c->h_mask + 2 * qmps_ctx::kMaskSlot;           // (third slot: never one of the two upload slots)
+  std::vector<unsigned char> was(T, 1);
+  if (hm != nullptr) was.assign(hm, hm + T);
+  for (int64_t t = 0; t < T; ++t) fix[t] = (was[t] != 0 && (st[t] == qmps::QMPS_ST_NOT_CONVERGED || st[T + t] == qmps::QMPS_ST_NOT_CONVERGED)) ? 1 : 0;
+  for (int64_t t = T; t < (T + 7) / 8 * 8; ++t) fix[t] = 0;
+  HIP_TRY(qmps::launch_overlap_krylov_pair(c->D, gp.a, gp.l, c->stream));
+  HIP_TRY(qmps::launch_stage_copy(fix, c->d_active, (T + 7) / 8, c->stream));
+  gp.g.active = c->d_active;
+  HIP_TRY(qmps::launch_overlap_grad(c->D, gp.g, c->stream));
+  // the timed interval of this batch ends HERE when there was a second pass (Krylov pair, G, probes): kernel time, the evolve
+  // drivers' gradient_ms and kernel_share_of_wall count the fall-back too (the first read-back sits inside the interval: the
+  // cost of discovering the stragglers)
+  HIP_TRY(timer.extend());
+  return read_back(c, s);
+}
+// the probes on the host: f, the central differences and the worse status of the two solves of every iterate
+int finish_gradient(qmps_ctx* c, int64_t T, int P, double h, bool two_sided_f, const GradStaging& s, double* f_out, double* g_out, int32_t* status_out) {
+  const int32_t* st = s.st;
+  memcpy(f_out, s.f, (size_t)T * sizeof(double));
+  const double* fn = s.f + T;
   bool tied = false;
   for (int64_t t = 0; t < T; ++t) {
-    const int s = qmps::overlap_worse(st[t], st[T + t]);
-    if (status_out) status_out[t] = s;
+    const int status = qmps::overlap_worse(st[t], st[T + t]);
+    if (status_out) status_out[t] = status;
     // a TIED iterate (D = 4) has no fixed points: nothing to expand its neighbours round - no gradient (the callers eigen-solve them)
-    if (s == qmps::QMPS_ST_TIED) tied = true;
+    if (status == qmps::QMPS_ST_TIED) tied = true;
     for (int k = 0; k < P; ++k)
-      g_out[t * P + k] = s == qmps::QMPS_ST_TIED ? __builtin_nan("") : (fn[(size_t)t * 2 * P + k] - fn[(size_t)t * 2 * P + P + k]) / (2.0 * h);
+      g_out[t * P + k] = status == qmps::QMPS_ST_TIED ? __builtin_nan("") : (fn[(size_t)t * 2 * P + k] - fn[(size_t)t * 2 * P + P + k]) / (2.0 * h);
   }
-  if (tied && (flags & QMPS_OVERLAP_TWO_SIDED_F)) {
+  if (tied && two_sided_f) {
     // ... nor a two-sided quotient: its objective is the solve's own common modulus, which the quotient of the two mixtures overwrote in
     // d_f - back from the right solve's eta as overlap_store computes it (a batch without a tie never gets here)
     std::vector<double> eta((size_t)2 * T);
@@ -632,6 +672,50 @@ int qmps_overlap_gradient(qmps_ctx* c, int64_t T, int kind, int n_params, const 
       if (qmps::overlap_worse(st[t], st[T + t]) == qmps::QMPS_ST_TIED)
         f_out[t] = -__builtin_sqrt(__builtin_sqrt(eta[2 * t] * eta[2 * t] + eta[2 * t + 1] * eta[2 * t + 1]));
   }
+  return QMPS_OK;
+}
+}  // namespace
+
+int qmps_overlap_gradient(qmps_ctx* c, int64_t T, int kind, int n_params, const double* params, double h, int max_rounds, double tol,
+                          int flags, double* f_out, double* g_out, int32_t* status_out) try {
+  if (int rc = bind(c)) return rc;
+  DisarmOneShots disarm{c};      // (one-shot mask: spent on every way out)
+  const OverlapRoute route = overlap_route(c);
+  if (!params || !f_out || !g_out) return fail(QMPS_ERR_ARG, "null argument");
+  if (c->D < 4) return fail(QMPS_ERR_ARG, "qmps_overlap_gradient: D = 4, 8, 16 (at D = 2 evaluate the central-difference neighbours themselves)");
+  if (flags & ~(QMPS_OVERLAP_WARM | QMPS_OVERLAP_TWO_SIDED_F)) return fail(QMPS_ERR_ARG, "unknown flag bits 0x%x", flags);
+  if (!(h > 0.0)) return fail(QMPS_ERR_ARG, "h must be > 0");
+  const int P = n_params;
+  if (T < 1 || T * (1 + 2 * (int64_t)P) > c->max_batch) return fail(QMPS_ERR_ARG, "T (1 + 2 n_params) = %lld evaluations exceed max_batch = %lld", (long long)(T * (1 + 2 * (int64_t)P)), (long long)c->max_batch);
+  if (c->overlap_refs < T) return fail(QMPS_ERR_STATE, "%lld reference tensors resident, %lld trajectories (qmps_overlap_set / qmps_overlap_set_refs_ansatz)", (long long)c->overlap_refs, (long long)T);
+  if (max_rounds < 1 || max_rounds > (1 << 24) || !(tol > 0.0)) return fail(QMPS_ERR_ARG, "bad max_rounds / tol");
+  const bool warm = (flags & QMPS_OVERLAP_WARM) != 0, two_sided_f = (flags & QMPS_OVERLAP_TWO_SIDED_F) != 0;
+  if (warm && c->grad_warm_T != T) return fail(QMPS_ERR_STATE, "QMPS_OVERLAP_WARM: the resident fixed points belong to %lld trajectories, not %lld", (long long)c->grad_warm_T, (long long)T);
+  if (int rc = ensure_gradient_buffers(c, T)) return rc;
+  GradStaging staging;
+  if (int rc = ensure_staging(c, T, P, staging)) return rc;
+  // the 2 P central-difference neighbours of every iterate (evaluated below to second order in h from (y, r)): neighbour_build
+  const bool beside = neighbour_build(c, route, T, kind, P) == NeighbourBuild::Beside;
+  if (int rc = upload_iterates(c, T, kind, P, params, beside)) return rc;
+  const unsigned char* mask;
+  if (int rc = take_mask(c, 0, T, &mask)) return rc;
+  // HIP events around the WHOLE gradient evaluation (right solve, left solve, neighbour tensors, G, probes): qmps_kernel_time
+  KernelTimer timer(c, periodic_timing(c));
+  HIP_TRY(timer.start());
+  if (beside && c->fork_after_copy) {        // (the parameter upload took another path: it did not record the fork)
+    c->fork_after_copy = nullptr;
+    return fail(QMPS_ERR_STATE, "qmps_overlap_gradient: the parameter upload did not record the fork event");
+  }
+  GradPass gp;
+  const double* tol_in = c->grad_tol_in;        // one-shot (qmps_evolve_bfgs, host loop): per-trajectory tolerances
+  c->grad_tol_in = nullptr;
+  if (int rc = enqueue_gradient_kernels(c, route, T, kind, P, c->d_params, h, max_rounds, tol, warm, two_sided_f, mask, true, gp, tol_in)) return rc;
+  HIP_TRY(timer.stop());
+  c->launches++;
+  if (int rc = read_back(c, staging)) return rc;
+  if (gp.lazy_krylov)
+    if (int rc = krylov_second_pass(c, T, mask, gp, timer, staging)) return rc;
+  if (int rc = finish_gradient(c, T, P, h, two_sided_f, staging, f_out, g_out, status_out)) return rc;
   c->window = 0;
   forget_resident_state(c);
   c->grad_warm_T = T;

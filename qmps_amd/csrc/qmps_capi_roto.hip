@@ -1,7 +1,7 @@
 // qmps_capi_roto.hip - the rotosolve drivers of the C-ABI (declared in include/qmps_hip.h): qmps_rotosolve / qmps_double_rotosolve on the
 // energy (a function per path: the whole-run kernels of D = 2 and D = 8, the step-by-step path with its cached sweep graph) and
 // qmps_evolve_rotosolve on the time-evolution overlap objective, on the same work buffers and sweep-graph plumbing.  The launches they
-// enqueue: qmps_capi_energy.hip, qmps_capi_overlap.hip; the BFGS evolve drivers: qmps_capi_evolve.hip; context + helpers: qmps_capi.hip,
+// enqueue: qmps_capi_energy.hip, qmps_capi_overlap.hip (the overlap launches on the kernel route of the call: overlap_route); the BFGS evolve drivers: qmps_capi_evolve.hip; context + helpers: qmps_capi.hip,
 // qmps_ctx.h.
 #include "qmps_ctx.h"
 #include "qmps_overlap_internal.h"
@@ -235,7 +235,7 @@ int rotosolve_impl(qmps_ctx* c, int64_t R, int kind, int n_params, double* param
 
 // The time steps of qmps_evolve_rotosolve: r.R trajectories, r.max_iter = max_rounds of the overlap solves; slot_bytes: one warm-start
 // slot (0: the solver squares, no warm start).  The sweep graph is the caller's to destroy, once the stream has drained.
-int evolve_run(qmps_ctx* c, const RotoRun& r, int n_steps, size_t slot_bytes, double* params, const double* WW, double* params_hist, double* f_hist,
+int evolve_run(qmps_ctx* c, const OverlapRoute& route, const RotoRun& r, int n_steps, size_t slot_bytes, double* params, const double* WW, double* params_hist, double* f_hist,
                hipGraph_t* graph, hipGraphExec_t* exec) {
   const int64_t T = r.R;
   const int P = r.P;
@@ -262,7 +262,7 @@ int evolve_run(qmps_ctx* c, const RotoRun& r, int n_steps, size_t slot_bytes, do
       a.x_in = c->d_xwarm; a.r_out = c->d_xwarm;
       a.slot_ptr = shifts > 0 ? r.idx : r.idx + 3; a.slot_stride = (int64_t)slot_bytes;
     }
-    return launch_overlap_kernels(c, a);
+    return launch_overlap_kernels(c, route, a);
   };
   auto one_sweep = [&]() -> int {
     for (int i = 0; i < P; ++i) {
@@ -310,13 +310,13 @@ QMPS_API_CATCH
 int qmps_evolve_rotosolve(qmps_ctx* c, int64_t T, int kind, int n_params, double* params, const double* WW, int n_steps,
                           int n_sweeps, int nsh, int max_rounds, double tol, double* params_hist, double* f_hist) try {
   if (int rc = bind(c)) return rc;
+  const OverlapRoute route = overlap_route(c);
   if (!params || !WW || !f_hist) return fail(QMPS_ERR_ARG, "null argument");
   if (nsh != 3 && nsh != 6) return fail(QMPS_ERR_ARG, "nsh must be 3 (single-frequency) or 6 (double-frequency)");
   if (T < 1 || nsh * T > c->max_batch) return fail(QMPS_ERR_ARG, "%d T = %lld candidates exceed max_batch = %lld", nsh, (long long)(nsh * T), (long long)c->max_batch);
   if (n_steps < 1 || n_sweeps < 1) return fail(QMPS_ERR_ARG, "n_steps and n_sweeps must be >= 1");
   if (int rc = check_ansatz(c, kind, n_params)) return rc;
-  const bool squaring = overlap_squares(c);
-  const int cap = squaring ? 60 : (1 << 24);
+  const int cap = route.squares ? 60 : (1 << 24);
   if (max_rounds < 1 || max_rounds > cap || !(tol > 0.0)) return fail(QMPS_ERR_ARG, "bad max_rounds / tol (D = %d: max_rounds in [1, %d])", c->D, cap);
   const size_t vec_bytes = (size_t)T * n_params * sizeof(double);
   if (int rc = ready_buffers(c, vec_bytes, (size_t)T * n_steps * n_sweeps * sizeof(double))) return rc;
@@ -327,7 +327,7 @@ int qmps_evolve_rotosolve(qmps_ctx* c, int64_t T, int kind, int n_params, double
   // fixed points of the power method (D = 8, 16), one set per parameter plus one for the unshifted evaluation of a sweep:
   // the candidates of parameter i come back to the same slot in the next sweep and in the next time step - by then the
   // parameters have moved by one sweep's updates, so the resident fixed point is the natural warm start
-  const size_t slot_bytes = squaring ? 0 : (size_t)nsh * T * env_bytes(c);
+  const size_t slot_bytes = route.squares ? 0 : (size_t)nsh * T * env_bytes(c);
   if (slot_bytes) {
     if (int rc = grow(c->d_xwarm, c->xwarm_bytes, (size_t)(n_params + 1) * slot_bytes)) return rc;
     HIP_TRY(hipMemsetAsync(c->d_xwarm, 0, (size_t)(n_params + 1) * slot_bytes, c->stream));       // all zero = cold start
@@ -335,7 +335,7 @@ int qmps_evolve_rotosolve(qmps_ctx* c, int64_t T, int kind, int n_params, double
   const RotoRun r{T, kind, n_params, n_sweeps, max_rounds, tol, nsh, c->roto_base, c->roto_hist, c->roto_idx};
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
-  const int rc = evolve_run(c, r, n_steps, slot_bytes, params, WW, params_hist, f_hist, &graph, &exec);
+  const int rc = evolve_run(c, route, r, n_steps, slot_bytes, params, WW, params_hist, f_hist, &graph, &exec);
   (void)hipStreamSynchronize(c->stream);
   if (exec) (void)hipGraphExecDestroy(exec);
   if (graph) (void)hipGraphDestroy(graph);

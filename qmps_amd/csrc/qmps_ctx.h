@@ -5,9 +5,9 @@
 //   qmps_capi_cost.hip       the summed-cost exchange and its RCCL communicator (setup_accumulator, close_group)
 //   qmps_capi_brickwall.hip  the brick-wall calls
 //   qmps_capi_probe.hip      the peak probes
-//   qmps_capi_overlap.hip    the time-evolution overlap objective and its gradient
-//   qmps_capi_evolve.hip     the BFGS evolve drivers
-//   qmps_capi_roto.hip       the rotosolve drivers of the energy and of the overlap objective
+//   qmps_capi_overlap.hip    the time-evolution overlap objective and its gradient; overlap_route (qmps_overlap_internal.h): which kernels they run
+//   qmps_capi_evolve.hip     the BFGS evolve drivers (take the route of their call)
+//   qmps_capi_roto.hip       the rotosolve drivers of the energy and of the overlap objective (the latter takes the route of its call)
 //   qmps_capi_observables.hip  observables of the resident states: two-point functions, Schmidt spectra, correlator sums
 #pragma once
 #include <hip/hip_runtime.h>

@@ -58,6 +58,27 @@ def test_the_overlap_dispatch_file_holds_no_kernels():
         assert '__global__' in src[f], f
 
 
+def test_the_overlap_switches_are_read_in_overlap_route_only():
+    """The host code of the overlap side (objective, gradient, BFGS and rotosolve drivers) takes its kernel route from
+    overlap_route(): outside that function the five switch names occur in comments only."""
+    switches = ('QMPS_D16_BLOCK', 'QMPS_D16_ONE_WAVE', 'QMPS_NO_KRYLOV', 'QMPS_NO_DEFLATION', 'QMPS_OVERLAP_POWER')
+    src = sources()
+    text = src['qmps_capi_overlap.hip']
+    start = text.index('OverlapRoute overlap_route(const qmps_ctx* c) {')
+    end = text.index('\n}\n', start)
+    route = text[start:end]
+    for name in switches:
+        assert 'documented_switch("%s")' % name in route, name
+    executable = {'qmps_capi_overlap.hip': text[:start] + text[end:], 'qmps_capi_evolve.hip': src['qmps_capi_evolve.hip'],
+                  'qmps_capi_roto.hip': src['qmps_capi_roto.hip']}
+    for f, code in executable.items():
+        assert '/*' not in code, f
+        code = re.sub(r'//.*', '', code)
+        for name in switches:
+            assert name not in code, (f, name)
+    assert 'overlap_squares' not in ''.join(src.values())
+
+
 def test_the_correlator_sum_dispatch_file_holds_no_kernels_and_no_kernel_asks_for_the_source():
     """qmps_corrsum.hip checks the arguments and chooses the kernel family; the source of the right-hand sides is a type the kernels
     are instantiated with (OneSiteSource, TwoSiteSource), never a value they branch on."""

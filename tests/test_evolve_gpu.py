@@ -171,6 +171,38 @@ def test_two_sided_gradient_with_separate_d16_solves_vs_oracle(T, engine_factory
                 assert abs(gv[k] - g_ref) < 2e-7, (t, k, gv[k], g_ref)
 
 
+@pytest.mark.parametrize('D,P,switch,max_rounds', [(16, 8, 'QMPS_D16_BLOCK', None), (4, 4, 'QMPS_OVERLAP_POWER', 100000)])
+def test_two_sided_gradient_with_separate_block_kernel_solves_vs_oracle(D, P, switch, max_rounds, engine_factory, monkeypatch):
+    """The other two ways onto the "two separate launches" route of qmps_overlap_gradient: QMPS_D16_BLOCK (D = 16) and
+    QMPS_OVERLAP_POWER (D = 4: power steps, so max_rounds is the power-step cap, not the squaring cap of 60) - the right and the left
+    fixed points from one overlap_block_kernel<D> launch each.  Cold, then warm at moved parameters; objective and gradient against
+    the oracle's central differences of dense eigen-solves."""
+    T, h = 3, 1e-6
+    rng = np.random.default_rng(1700 + D)
+    WW = WW_of(0.05)
+    ref = rng.standard_normal((T, P))
+    X = ref + 0.03 * rng.standard_normal((T, P))
+    eng = engine_factory(D, 4096)
+    monkeypatch.setenv(switch, '1')
+    eng.overlap_set_refs_params(0, ref, WW)
+    eng.overlap_stats(reset=True)
+    f, g, st = eng.overlap_gradient(0, X, h=h, max_rounds=max_rounds, tol=1e-13)
+    assert np.all(st == 0) and eng.overlap_stats(reset=True)['evaluations'] == 2 * T
+    X2 = X + 1e-3 * rng.standard_normal(X.shape)
+    f2, g2, st2 = eng.overlap_gradient(0, X2, h=h, max_rounds=max_rounds, tol=1e-13, warm=True)
+    monkeypatch.delenv(switch)
+    assert np.all(st2 == 0)
+    for t in range(T):
+        A = ER.tensor(0, D, ref[t])
+        for x, fv, gv in ((X[t], f[t], g[t]), (X2[t], f2[t], g2[t])):
+            assert abs(fv - ER.objective(0, D, A, x, WW)) < 1e-10, (t, fv)
+            for k in (0, P - 1):
+                e = np.zeros(P)
+                e[k] = h
+                g_ref = (ER.objective(0, D, A, x + e, WW) - ER.objective(0, D, A, x - e, WW)) / (2 * h)
+                assert abs(gv[k] - g_ref) < 2e-7, (t, k, gv[k], g_ref)
+
+
 # (D, ansatz kind, parameters, trajectories, steps, sweeps, shifts per parameter, seed)
 ROTO_CASES = [(2, 2, 15, 3, 3, 2, 3, 11),      # the reference's own case: ShallowFullStateTensor(2, .), new_time_evolve.py:186-187
               (2, 0, 8, 3, 3, 2, 6, 12),       # scripts/loschmidt.py:203-207: ShallowCNOTStateTensor(2, .) with 8 angles, double frequency
