@@ -29,28 +29,6 @@ int bind(qmps_ctx* c) {
   return QMPS_OK;
 }
 
-int ensure_scratch(qmps_ctx* c, size_t bytes) {
-  if (bytes > c->scratch_bytes) {
-    if (c->d_scratch) HIP_TRY(hipFree(c->d_scratch));
-    c->d_scratch = nullptr;
-    c->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&c->d_scratch, bytes));
-    c->scratch_bytes = bytes;
-  }
-  return QMPS_OK;
-}
-
-int ensure_E(qmps_ctx* c, int n_terms) {
-  const int64_t need = c->max_batch * n_terms;
-  if (need > c->E_capacity) {
-    if (c->d_E) HIP_TRY(hipFree(c->d_E));
-    c->d_E = nullptr;
-    HIP_TRY(hipMalloc((void**)&c->d_E, (size_t)need * sizeof(double)));
-    c->E_capacity = need;
-  }
-  return QMPS_OK;
-}
-
 int check_B(const qmps_ctx* c, int64_t B) {
   if (B < 0 || B > c->max_batch) return fail(QMPS_ERR_ARG, "B=%lld outside [0, max_batch=%lld]", (long long)B, (long long)c->max_batch);
   return QMPS_OK;
@@ -60,6 +38,12 @@ int check_B(const qmps_ctx* c, int64_t B) {
 int check_window(const qmps_ctx* c, int64_t B) {
   if (B < 0 || c->window + B > c->max_batch)
     return fail(QMPS_ERR_ARG, "window [%lld, %lld) outside [0, max_batch=%lld]", (long long)c->window, (long long)(c->window + B), (long long)c->max_batch);
+  return QMPS_OK;
+}
+
+int check_resident(const qmps_ctx* c, int64_t B) {
+  if (c->window + B > c->states.count)
+    return fail(QMPS_ERR_STATE, "window [%lld, %lld) but only %lld states are resident", (long long)c->window, (long long)(c->window + B), (long long)c->states.count);
   return QMPS_OK;
 }
 
@@ -110,10 +94,11 @@ int check_ansatz(const qmps_ctx* c, int kind, int n_params) {
 
 // d_A <- tensors of the resident ansatz parameters, if nothing has built them yet
 int ensure_tensors(qmps_ctx* c) {
-  if (c->tensors_valid) return QMPS_OK;
-  if (!c->ans_have || c->ans_nsh != 0) return fail(QMPS_ERR_STATE, "no resident states");
-  HIP_TRY(qmps::launch_ansatz(c->D, c->ans_kind, c->ans_src ? c->ans_src : c->d_params, c->ans_P, c->d_A, c->n_states, c->stream));
-  c->tensors_valid = true;
+  const ResidentStates& s = c->states;
+  if (s.has_tensors) return QMPS_OK;
+  if (!s.ansatz || s.shifts != 0) return fail(QMPS_ERR_STATE, "no resident states");
+  HIP_TRY(qmps::launch_ansatz(c->D, s.kind, s.borrowed() ? s.rows : c->d_params, s.P, c->d_A, s.count, c->stream));
+  c->states.tensors_built();
   return QMPS_OK;
 }
 
@@ -317,19 +302,17 @@ int qmps_set_states(qmps_ctx* c, int64_t B, const double* states, int kind) try 
   }
   // the caller's host buffer may be pageable and re-used right after the call returns
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->n_states = B;
+  c->states.hold_tensors(B);
   c->window = 0;
   c->have_guess = false;
   forget_results(c);
-  c->ans_have = false;
-  c->tensors_valid = true;
   return QMPS_OK;
 }
 QMPS_API_CATCH
 
 int qmps_set_window(qmps_ctx* c, int64_t first) try {
   if (!c) return fail(QMPS_ERR_ARG, "null context");
-  if (first < 0 || first > c->n_states) return fail(QMPS_ERR_ARG, "window start %lld outside the %lld resident states", (long long)first, (long long)c->n_states);
+  if (first < 0 || first > c->states.count) return fail(QMPS_ERR_ARG, "window start %lld outside the %lld resident states", (long long)first, (long long)c->states.count);
   c->window = first;
   c->partials_B = -1;
   return QMPS_OK;
@@ -341,12 +324,7 @@ int qmps_set_states_ansatz(qmps_ctx* c, int64_t B, int kind, int n_params, const
   if (int rc = check_B(c, B)) return rc;
   if (!params && B > 0) return fail(QMPS_ERR_ARG, "null params");
   if (int rc = check_ansatz(c, kind, n_params)) return rc;
-  if (n_params > c->params_cap) {
-    if (c->d_params) HIP_TRY(hipFree(c->d_params));
-    c->d_params = nullptr;
-    HIP_TRY(hipMalloc((void**)&c->d_params, (size_t)c->max_batch * n_params * sizeof(double)));
-    c->params_cap = n_params;
-  }
+  if (int rc = ensure_params(c, n_params)) return rc;
   {
     const size_t pb = (size_t)B * n_params * sizeof(double);
     if (c->defer_sync && pb <= (8u << 20)) {
@@ -368,9 +346,7 @@ int qmps_set_states_ansatz(qmps_ctx* c, int64_t B, int kind, int n_params, const
       c->fork_after_copy = nullptr;
     }
   }
-  c->ans_have = true; c->ans_kind = kind; c->ans_P = n_params; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
-  c->tensors_valid = false;
-  c->n_states = B;
+  c->states.hold_ansatz(B, kind, n_params);
   // D = 4: the direct kernel builds the tensors itself (8 P bytes per evaluation instead of 512); d_A is filled on demand
   if (!fusable_ansatz(c, kind))
     if (int rc = ensure_tensors(c)) return rc;
@@ -387,21 +363,14 @@ int qmps_set_states_su(qmps_ctx* c, int64_t B, const double* params) try {
   if (int rc = check_B(c, B)) return rc;
   if (!params && B > 0) return fail(QMPS_ERR_ARG, "null params");
   const int N = 2 * c->D, np_ = N * N - 1;
-  if (np_ > c->params_cap) {
-    if (c->d_params) HIP_TRY(hipFree(c->d_params));
-    c->d_params = nullptr;
-    HIP_TRY(hipMalloc((void**)&c->d_params, (size_t)c->max_batch * np_ * sizeof(double)));
-    c->params_cap = np_;
-  }
+  if (int rc = ensure_params(c, np_)) return rc;
   HIP_TRY(hipMemcpyAsync(c->d_params, params, (size_t)B * np_ * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(qmps::launch_su_exp(N, c->d_params, B, np_, c->d_A, 1, c->stream));
   if (!c->defer_sync) HIP_TRY(hipStreamSynchronize(c->stream));
-  c->n_states = B;
+  c->states.hold_tensors(B);
   c->window = 0;
   c->have_guess = false;
   forget_results(c);
-  c->ans_have = false;
-  c->tensors_valid = true;
   return QMPS_OK;
 }
 QMPS_API_CATCH
@@ -426,7 +395,7 @@ int qmps_get_states(qmps_ctx* c, int64_t B, double* A) try {
   if (int rc = bind(c)) return rc;
   if (int rc = check_B(c, B)) return rc;
   if (!A) return fail(QMPS_ERR_ARG, "null A");
-  if (B > c->n_states) return fail(QMPS_ERR_STATE, "only %lld states are resident", (long long)c->n_states);
+  if (B > c->states.count) return fail(QMPS_ERR_STATE, "only %lld states are resident", (long long)c->states.count);
   if (int rc = ensure_tensors(c)) return rc;
   HIP_TRY(hipMemcpyAsync(A, c->d_A, (size_t)B * tensor_bytes(c), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

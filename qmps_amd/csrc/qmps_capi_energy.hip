@@ -234,7 +234,7 @@ EnergyPathFn energy_path(const qmps_ctx* c, int solver, int max_iter) {
 int qmps_energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int flags) try {
   if (int rc = bind(c)) return rc;
   if (int rc = check_window(c, B)) return rc;
-  if (c->window + B > c->n_states) return fail(QMPS_ERR_STATE, "window [%lld, %lld) but only %lld states are resident", (long long)c->window, (long long)(c->window + B), (long long)c->n_states);
+  if (int rc = check_resident(c, B)) return rc;
   if (c->n_terms < 1) return fail(QMPS_ERR_STATE, "qmps_set_hamiltonian has not been called");
   if (max_iter < 1) return fail(QMPS_ERR_ARG, "max_iter must be >= 1");
   if (!(tol > 0.0)) return fail(QMPS_ERR_ARG, "tol must be > 0");
@@ -258,16 +258,17 @@ int qmps_energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int fla
   c->acc_pending = false;   // whatever an earlier launch accumulated no longer describes the resident energies
   c->have_overlap_x = false;   // d_r is about to hold environments, not overlap fixed points
   c->grad_warm_T = 0;
-  const bool fused = direct && c->ans_have && fusable_ansatz(c, c->ans_kind);   // the direct kernel builds the tensors itself
+  const ResidentStates& s = c->states;
+  const bool fused = direct && s.ansatz && fusable_ansatz(c, s.kind);   // the direct kernel builds the tensors itself
   if (!fused)
     if (int rc = ensure_tensors(c)) return rc;
   qmps::LaneArgs a = make_args(c, B, max_iter, tol, true);
   // (a window none of whose slots was ever stored or guessed starts cold, as documented: its part of d_r holds whatever was there)
   if (warm_resident) a.r_in = window_has_start(c, B) ? win_r(c) : nullptr;
   if (fused) {
-    const double* rows = c->ans_src ? c->ans_src : c->d_params;
-    a.ans_params = c->ans_nsh > 0 ? rows : rows + (size_t)c->window * c->ans_P;
-    a.ans_P = c->ans_P; a.ans_kind = c->ans_kind; a.ans_nsh = c->ans_nsh; a.ans_i = c->ans_i;
+    const double* rows = s.borrowed() ? s.rows : c->d_params;
+    a.ans_params = s.shifts > 0 ? rows : rows + (size_t)c->window * s.P;
+    a.ans_P = s.P; a.ans_kind = s.kind; a.ans_nsh = s.shifts; a.ans_i = s.shift_index;
   }
   c->partials_B = -1;
   KernelTimer timer(c, periodic_timing(c));
@@ -300,7 +301,7 @@ QMPS_API_CATCH
 int qmps_energy_only_launch(qmps_ctx* c, int64_t B) try {
   if (int rc = bind(c)) return rc;
   if (int rc = check_window(c, B)) return rc;
-  if (c->window + B > c->n_states) return fail(QMPS_ERR_STATE, "window [%lld, %lld) but only %lld states are resident", (long long)c->window, (long long)(c->window + B), (long long)c->n_states);
+  if (int rc = check_resident(c, B)) return rc;
   if (c->n_terms < 1) return fail(QMPS_ERR_STATE, "qmps_set_hamiltonian has not been called");
   if (!c->env.covers(c->window, c->window + B))
     return fail(QMPS_ERR_STATE, "no resident environment for the window [%lld, %lld): run qmps_energy_launch (storing them) or qmps_set_env_guess over it first", (long long)c->window, (long long)(c->window + B));
@@ -495,7 +496,7 @@ int cell2_run(qmps_ctx* c, int64_t B, int n_terms, int max_iter, double tol, dou
   a.iters = c->d_iters; a.status = c->d_status; a.B = B; a.n_terms = n_terms; a.max_iter = max_iter; a.tol = tol;
   c->partials_B = -1;
   HIP_TRY(qmps::launch_cell2(c->D, a, c->stream));
-  c->n_states = 0;  // the resident single-site states (if any) are no longer what d_E refers to
+  c->states.hold_tensors(0);  // the resident single-site states (if any) are no longer what d_E refers to
   forget_results(c);
   c->energies.add(0, B);      // the unit cell's own energies, iteration counts and statuses, at the start of the buffers
   c->counts.add(0, B);

@@ -83,12 +83,8 @@ int evolve_bfgs_device_algebra(const BfgsGroup& job, BfgsRun& run) {
     const size_t n_ctl = 16 + 2 * ((size_t)maxiter + 2);
     const size_t n_dbl = 4 * TP + TP * P + 6 * (size_t)T + (size_t)n_steps * 2 * T + (size_t)n_steps * TP + (size_t)NA + (size_t)T * (G > 0 ? G : 1) * P;
     const size_t bytes = n_dbl * sizeof(double) + (n_ctl + (n_ctl & 1)) * sizeof(int) + 3 * (((size_t)T + 7) / 8 * 8) + 64;
-    if (bytes > c->d_lock_bytes) {
-      if (c->d_lock) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_lock)); }
-      c->d_lock = nullptr; c->d_lock_bytes = 0;
-      HIP_TRY(hipMalloc(&c->d_lock, bytes));
-      c->d_lock_bytes = bytes;
-    }
+    if (bytes > c->d_lock_bytes && c->d_lock) HIP_TRY(hipStreamSynchronize(c->stream));      // (kernels of an earlier call may still be at work in it)
+    if ((rc = grow(c->d_lock, c->d_lock_bytes, bytes))) return rc;
     double* q = (double*)c->d_lock;
     dv.X = q; q += TP; dv.G = q; q += TP; dv.Dv = q; q += TP; dv.Xc = q; q += TP;
     dv.H = q; q += TP * P; dv.F = q; q += T; dv.slope = q; q += T; dv.F0 = q; q += T; dv.asel = q; q += T; dv.tolarr = q; q += T; dv.g0max = q; q += T;
@@ -112,7 +108,7 @@ int evolve_bfgs_device_algebra(const BfgsGroup& job, BfgsRun& run) {
     HIP_TRY(hipStreamSynchronize(c->stream));       // (X, Hinv, tol0 are pageable host vectors)
     c->window = 0;
     forget_resident_state(c);
-    c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0; c->tensors_valid = false; c->n_states = 0;
+    c->states.hold_nothing();
   }
   const bool beside = neighbour_build(c, run.route, T, kind, P) == NeighbourBuild::Beside;
   auto lock_args = [&](int step, bool reset_h, int mode) {
@@ -180,13 +176,13 @@ int evolve_bfgs_device_algebra(const BfgsGroup& job, BfgsRun& run) {
       HIP_TRY(qmps::launch_lockstep_ladder_cand(la, c->stream));
       HIP_TRY(hipMemcpyAsync(c->d_active, dv.need, (size_t)T, hipMemcpyDeviceToDevice, c->stream));
       c->mask_stash_n = 0; c->mask_host = nullptr; c->active_n = T;
-      c->ans_have = true; c->ans_kind = kind; c->ans_P = P; c->ans_src = dv.cand; c->ans_i = nullptr; c->ans_nsh = 0;
-      c->tensors_valid = false; c->n_states = T * G; c->window = 0;
+      c->states.hold_ansatz(T * G, kind, P, dv.cand);
+      c->window = 0;
       c->overlap_group = G;
       c->warm_from_group = (c->grad_warm_T == T) ? G : 0;      // (resident: the fixed points of the rejected full steps)
       const int e = qmps_overlap_launch(c, T * G, run.ladder_rounds, tol, 0);
       c->overlap_group = 0;
-      c->ans_have = false; c->ans_src = nullptr; c->tensors_valid = false; c->n_states = 0;
+      c->states.hold_nothing();
       if (e) return e;
       HIP_TRY(qmps::launch_lockstep_ladder_pick(la, c->d_f, c->d_status, c->stream));
       if (int e2 = dev_gradient(dv.Xc, dv.need)) return e2;

@@ -20,8 +20,7 @@ int resident_front(qmps_ctx* c, int64_t B, uint64_t bytes_per_eval, const char* 
   if (bytes_per_eval > 0 && (uint64_t)B > kLimit / bytes_per_eval)
     return fail(QMPS_ERR_ARG, "result of %lld x %llu bytes exceeds the limit of 1 GiB (2^30 bytes): split the batch or %s", (long long)B,
                 (unsigned long long)bytes_per_eval, other_axis);
-  if (c->window + B > c->n_states)
-    return fail(QMPS_ERR_STATE, "window [%lld, %lld) but only %lld states are resident", (long long)c->window, (long long)(c->window + B), (long long)c->n_states);
+  if (int rc = check_resident(c, B)) return rc;
   if (!c->env.covers(c->window, c->window + B)) return fail(QMPS_ERR_STATE, "no resident environment for the window: run qmps_energy_launch (without QMPS_FLAG_NO_ENV_OUT) or qmps_set_env_guess first");
   empty = B == 0;
   return QMPS_OK;

@@ -14,16 +14,7 @@ using namespace qmps_host;
 // (every entry point below is declared extern "C" in include/qmps_hip.h: the definitions inherit the linkage)
 
 namespace qmps_host {
-int ensure_refs(qmps_ctx* c, int64_t n_ref) {
-  if (n_ref > c->ref_cap) {
-    if (c->d_ref) HIP_TRY(hipFree(c->d_ref));
-    c->d_ref = nullptr;
-    c->ref_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_ref, (size_t)n_ref * tensor_bytes(c)));
-    c->ref_cap = n_ref;
-  }
-  return QMPS_OK;
-}
+int ensure_refs(qmps_ctx* c, int64_t n_ref) { return grow(c->d_ref, c->ref_cap, n_ref, (size_t)n_ref * tensor_bytes(c)); }
 int set_ww(qmps_ctx* c, const double* WW) {
   if (!c->d_ww) HIP_TRY(hipMalloc(&c->d_ww, 256));
   HIP_TRY(hipMemcpyAsync(c->d_ww, WW, 256, hipMemcpyHostToDevice, c->stream));
@@ -270,7 +261,7 @@ int qmps_overlap_launch(qmps_ctx* c, int64_t B, int max_rounds, double tol, int 
   DisarmOneShots disarm{c};      // the mask of qmps_overlap_set_active is ONE-SHOT: spent on every way out
   const OverlapRoute route = overlap_route(c);
   if (int rc = check_window(c, B)) return rc;
-  if (c->window + B > c->n_states) return fail(QMPS_ERR_STATE, "window [%lld, %lld) but only %lld states are resident", (long long)c->window, (long long)(c->window + B), (long long)c->n_states);
+  if (int rc = check_resident(c, B)) return rc;
   if (c->overlap_refs < 1) return fail(QMPS_ERR_STATE, "qmps_overlap_set has not been called");
   if (flags & ~(QMPS_OVERLAP_WANT_R | QMPS_OVERLAP_WARM)) return fail(QMPS_ERR_ARG, "unknown flag bits 0x%x", flags);
   const bool want_r = (flags & QMPS_OVERLAP_WANT_R) != 0, warm = (flags & QMPS_OVERLAP_WARM) != 0;
@@ -378,7 +369,7 @@ int qmps_overlap_amplitude(qmps_ctx* c, int64_t B, const double* q, double* amp_
   if (int rc = bind(c)) return rc;
   if (int rc = check_window(c, B)) return rc;
   if (!q || !amp_out) return fail(QMPS_ERR_ARG, "null argument");
-  if (c->window + B > c->n_states) return fail(QMPS_ERR_STATE, "window [%lld, %lld) but only %lld states are resident", (long long)c->window, (long long)(c->window + B), (long long)c->n_states);
+  if (int rc = check_resident(c, B)) return rc;
   if (c->overlap_refs < 1) return fail(QMPS_ERR_STATE, "qmps_overlap_set has not been called");
   if (int rc = check_group_alignment(c)) return rc;
   if (int rc = check_reference_cover(c, B)) return rc;

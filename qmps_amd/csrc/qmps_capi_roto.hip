@@ -27,18 +27,6 @@ struct RotoRun {
   int* idx;
 };
 
-template <class T>
-int grow(T*& buf, size_t& have, size_t need) {
-  if (need > have) {
-    if (buf) HIP_TRY(hipFree(buf));
-    buf = nullptr;
-    have = 0;
-    HIP_TRY(hipMalloc((void**)&buf, need));
-    have = need;
-  }
-  return QMPS_OK;
-}
-
 int ready_buffers(qmps_ctx* c, size_t base_bytes, size_t hist_bytes) {
   if (int rc = grow(c->roto_base, c->roto_base_bytes, base_bytes)) return rc;
   if (int rc = grow(c->roto_hist, c->roto_hist_bytes, hist_bytes)) return rc;
@@ -95,7 +83,7 @@ int whole_run(qmps_ctx* c, const RotoRun& r, hipError_t (*launch)(int, const qmp
   ra.skip = skip; ra.tol = r.tol; ra.direct = direct; ra.nsh = r.nsh; ra.rule = c->roto_rule;
   HIP_TRY(launch(r.kind, ra, c->stream));
   HIP_TRY(qmps::launch_ansatz(c->D, r.kind, r.base, r.P, c->d_A, r.R, c->stream));
-  c->n_states = r.R; c->ans_have = false; c->tensors_valid = true;
+  c->states.hold_tensors(r.R);
   forget_results(c);      // the launch below states what the R final vectors leave resident
   return qmps_energy_launch(c, r.R, r.max_iter, r.tol, c->default_solver);
 }
@@ -111,14 +99,12 @@ int step_by_step(qmps_ctx* c, const RotoRun& r) {
   auto evaluate = [&](int shifts) -> int {      // shifts = nsh: the shifted batch;  0: the R base vectors
     const int64_t n = shifts > 0 ? (int64_t)shifts * r.R : r.R;
     if (fused) {
-      c->ans_have = true; c->ans_kind = r.kind; c->ans_P = r.P; c->ans_src = r.base; c->ans_i = r.idx; c->ans_nsh = shifts;
-      c->tensors_valid = false;
+      c->states.hold_ansatz(n, r.kind, r.P, r.base, r.idx, shifts);      // (rows borrowed from the run: rotosolve_impl gives them back on every way out)
     } else {
       // shifted tensors straight from the base vectors (the shift build is folded into the ansatz kernel)
       HIP_TRY(qmps::launch_ansatz_shifted(c->D, r.kind, r.base, r.P, c->d_A, n, shifts, r.idx, c->stream));
-      c->ans_have = false; c->tensors_valid = true;
+      c->states.hold_tensors(n);
     }
-    c->n_states = n;
     return qmps_energy_launch(c, n, r.max_iter, r.tol, c->default_solver);
   };
   auto one_sweep = [&]() -> int {
@@ -153,7 +139,6 @@ int step_by_step(qmps_ctx* c, const RotoRun& r) {
   HIP_TRY(qmps::launch_roto_record(c->d_E, r.hist, (int)r.R, c->n_terms, r.idx + 2, 1, c->stream));
   // The context's view of what is resident - a replayed graph runs no host code, so it is stated here, not inherited from
   // the capture: the R final parameter vectors, their energies / statuses / environments
-  c->n_states = r.R;
   c->window = 0;
   forget_results(c);
   c->env.add(0, r.R); c->env_start.add(0, r.R); c->energies.add(0, r.R); c->counts.add(0, r.R);
@@ -162,11 +147,9 @@ int step_by_step(qmps_ctx* c, const RotoRun& r) {
   if (fused) {
     // as a qmps_set_states_ansatz of the final parameters would leave it: rows resident in d_params, tensors on demand
     HIP_TRY(hipMemcpyAsync(c->d_params, r.base, (size_t)r.R * r.P * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    c->ans_have = true; c->ans_kind = r.kind; c->ans_P = r.P; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
-    c->tensors_valid = false;
+    c->states.hold_ansatz(r.R, r.kind, r.P);
   } else {
-    c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
-    c->tensors_valid = true;
+    c->states.hold_tensors(r.R);
   }
   return QMPS_OK;
 }
@@ -210,21 +193,14 @@ int rotosolve_impl(qmps_ctx* c, int64_t R, int kind, int n_params, double* param
   if (n_sweeps < 1) return fail(QMPS_ERR_ARG, "n_sweeps must be >= 1");
   if (c->n_terms < 1) return fail(QMPS_ERR_STATE, "qmps_set_hamiltonian has not been called");
   if (int rc = check_ansatz(c, kind, n_params)) return rc;
-  if (n_params > c->params_cap) {
-    if (c->d_params) HIP_TRY(hipFree(c->d_params));
-    c->d_params = nullptr;
-    HIP_TRY(hipMalloc((void**)&c->d_params, (size_t)c->max_batch * n_params * sizeof(double)));
-    c->params_cap = n_params;
-  }
+  if (int rc = ensure_params(c, n_params)) return rc;
   if (int rc = ready_buffers(c, (size_t)R * n_params * sizeof(double), ((size_t)R * n_sweeps + kHistExtra) * sizeof(double))) return rc;
   const RotoRun r{R, kind, n_params, n_sweeps, max_iter, tol, nsh, c->roto_base, c->roto_hist, c->roto_idx};
   int rc = upload_and_run(c, r, params);
   // (the instrumented D = 8 kernel's clocks sit behind the history and come back with it)
   if (rc == QMPS_OK) rc = download_results(c, r, (size_t)R * n_sweeps + (kHistExtra && d8_whole_run(c, r) ? kHistExtra : 0), params, E_hist);
   (void)hipStreamSynchronize(c->stream);
-  if (c->ans_src != nullptr) {     // an error left the context pointing at the run's own buffers
-    c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0; c->ans_have = false; c->tensors_valid = true; c->n_states = 0;
-  }
+  if (c->states.borrowed()) c->states.hold_tensors(0);     // an error left the context pointing at the run's own buffers
   if (rc != QMPS_OK && c->roto_exec) {     // do not trust a sweep captured by a failed run
     (void)hipGraphExecDestroy(c->roto_exec);
     if (c->roto_graph) (void)hipGraphDestroy(c->roto_graph);
@@ -249,7 +225,7 @@ int evolve_run(qmps_ctx* c, const OverlapRoute& route, const RotoRun& r, int n_s
   c->window = 0;
   forget_resident_state(c);
   c->energies.clear();        // d_E is the run's objective buffer: what qmps_get_energies would return are overlap objectives
-  c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
+  c->states.hold_tensors(0);      // d_A is the run's candidate buffer from here on; the caller states what the run leaves
   auto evaluate = [&](int shifts) -> int {      // shifts = nsh: the shifted batch of parameter *idx;  0: the T base vectors
     const int64_t n = shifts > 0 ? (int64_t)shifts * T : T;
     HIP_TRY(qmps::launch_ansatz_shifted(c->D, r.kind, r.base, P, c->d_A, n, shifts, r.idx, c->stream));
@@ -340,8 +316,7 @@ int qmps_evolve_rotosolve(qmps_ctx* c, int64_t T, int kind, int n_params, double
   if (exec) (void)hipGraphExecDestroy(exec);
   if (graph) (void)hipGraphDestroy(graph);
   // what the call leaves resident: the T final candidates (tensors, eta, objective, status) against the last step's references
-  c->n_states = rc == QMPS_OK ? T : 0;
-  c->tensors_valid = true;
+  c->states.hold_tensors(rc == QMPS_OK ? T : 0);
   c->overlap_refs = rc == QMPS_OK ? T : 0;
   c->overlap_group = 0;
   return rc;

@@ -9,6 +9,16 @@
 //   qmps_capi_evolve.hip     the BFGS evolve drivers (take the route of their call)
 //   qmps_capi_roto.hip       the rotosolve drivers of the energy and of the overlap objective (the latter takes the route of its call)
 //   qmps_capi_observables.hip  observables of the resident states: two-point functions, Schmidt spectra, correlator sums
+// What is resident is stated in qmps_resident.h (free of HIP; tests/csrc/resident_check.cpp runs it on the host): `states`, a
+// ResidentStates, says what d_A / d_params hold and is assigned by its transitions only; the qmps_slots say which windows of
+// the result buffers hold what.  The entry points leave `states` in one of four forms:
+//   hold_tensors(n)     qmps_set_states, qmps_set_states_su, the whole-run and the unfused step-by-step rotosolve, qmps_evolve_rotosolve
+//                       (n = 0 when it fails), a rotosolve that fails with borrowed rows (0), the two-site unit cell (0); a fresh context (0)
+//   hold_ansatz(n, ..)  qmps_set_states_ansatz, the fused step-by-step rotosolve (rows in d_params); tensors_built() once ensure_tensors ran
+//   hold_ansatz(n, .., rows, ..)   borrowed rows, during a call only: the fused rotosolve's shift batches, the lock-step BFGS ladder
+//   hold_nothing()      the BFGS evolve drivers (forget_resident_candidates)
+// Device buffers that grow on demand go through grow() (ensure_scratch, ensure_E, ensure_params, ensure_refs, the rotosolve and
+// lock-step work buffers); ensure_pinned carries its contents over and stands alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -28,6 +38,7 @@
 #include "qmps_hip.h"
 #include "qmps_kernels.h"
 #include "qmps_knobs.h"
+#include "qmps_resident.h"
 
 namespace qmps_host {
 
@@ -65,49 +76,6 @@ constexpr int kSumBlocks = 256;
     ncclResult_t r_ = (expr);                                                                                    \
     if (r_ != ncclSuccess) return qmps_host::fail(QMPS_ERR_RCCL, "%s failed: %s", #expr, ncclGetErrorString(r_)); \
   } while (0)
-
-// Which evaluations of a resident array hold what a context-wide flag used to claim for all of them: a short list of disjoint
-// half-open intervals [lo, hi), sorted.  Launches and read-backs are windowed (qmps_set_window), so the facts about d_r, d_E, d_iters
-// and d_status are kept per slot: a launch adds its window, a call that overwrites or outdates slots removes them.
-struct qmps_slots {
-  std::vector<std::pair<int64_t, int64_t>> v;
-  void clear() { v.clear(); }
-  bool any() const { return !v.empty(); }
-  bool touches(int64_t lo, int64_t hi) const {
-    for (const auto& s : v)
-      if (s.second > lo && s.first < hi) return true;
-    return false;
-  }
-  void remove(int64_t lo, int64_t hi) {
-    if (hi <= lo || !touches(lo, hi)) return;      // (the common case on the hot path: nothing to do, nothing allocated)
-    std::vector<std::pair<int64_t, int64_t>> out;
-    for (const auto& s : v) {
-      if (s.second <= lo || s.first >= hi) { out.push_back(s); continue; }
-      if (s.first < lo) out.push_back({s.first, lo});
-      if (s.second > hi) out.push_back({hi, s.second});
-    }
-    v.swap(out);
-  }
-  void add(int64_t lo, int64_t hi) {
-    if (hi <= lo || covers(lo, hi)) return;        // (a step repeated over the same window: nothing to do, nothing allocated)
-    for (const auto& s : v) {          // swallow what touches [lo, hi)
-      if (s.second < lo || s.first > hi) continue;
-      if (s.first < lo) lo = s.first;
-      if (s.second > hi) hi = s.second;
-    }
-    remove(lo, hi);
-    size_t at = 0;
-    while (at < v.size() && v[at].first < lo) ++at;
-    v.insert(v.begin() + at, {lo, hi});
-  }
-  // an empty range is covered as soon as anything is resident (B = 0 calls keep the answer of the old flag)
-  bool covers(int64_t lo, int64_t hi) const {
-    if (hi <= lo) return any();
-    for (const auto& s : v)
-      if (s.first <= lo && hi <= s.second) return true;
-    return false;
-  }
-};
 
 struct qmps_ctx {
   int device = -1;
@@ -204,7 +172,10 @@ struct qmps_ctx {
   int matvec_period = QMPS_MATVEC_PERIOD_D4;   // D = 4: mat-vecs with T^(2^m) between two further squarings
   // state
   int n_terms = 0;
-  int64_t n_states = 0;
+  // what d_A / d_params hold (qmps_resident.h).  Ansatz-parametrised states: the parameters stay resident (d_params, or rows borrowed
+  // from a driver during its run); at D = 4 the direct kernel builds the tensor itself, so d_A is materialised only when something
+  // else asks for the tensors (ensure_tensors)
+  ResidentStates states;
   int64_t window = 0;               // first evaluation addressed by the launch / read-back calls (qmps_set_window)
   int64_t overlap_refs = 0;         // reference tensors resident for the overlap objective (1 = shared by the batch)
   bool have_guess = false;
@@ -218,12 +189,6 @@ struct qmps_ctx {
   bool have_overlap_x = false;       // d_r holds the fixed points of the last overlap launch (QMPS_OVERLAP_WANT_R)
   bool want_rho = false;
   bool defer_sync = false;          // one-shot entry points: the setters leave their H2D copies in flight, ONE synchronisation at the end
-  // ansatz-parametrised states: the parameters stay resident (d_params, or ans_src during a rotosolve run); at D = 4 the
-  // direct kernel builds the tensor itself, so d_A is materialised only when something else asks for the tensors
-  bool ans_have = false;            // the resident states ARE ansatz(kind, P) of the resident parameters
-  bool tensors_valid = true;        // d_A holds the tensors of the resident states
-  int ans_kind = 0, ans_P = 0;
-  const double* ans_src = nullptr;  // parameter rows (nullptr: d_params)
   // rotosolve work buffers and the captured sweep are kept between calls (a call used to spend ~0.6 ms on hipMalloc /
   // hipFree / graph capture + instantiation - as much as three sweeps at D = 4)
   double* roto_base = nullptr;
@@ -244,8 +209,6 @@ struct qmps_ctx {
              handoff == o.handoff && rule == o.rule && tol == o.tol && fused == o.fused && base == o.base && hist == o.hist && params == o.params && E == o.E;
     }
   } roto_key;
-  const int* ans_i = nullptr;       // rotosolve: device index of the parameter being updated
-  int ans_nsh = 0;                  // rotosolve: shifts per restart (0: one parameter row per evaluation)
   // RCCL: the all-reduce runs on its own stream so that it overlaps the next step's kernels
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -339,17 +302,36 @@ inline void forget_resident_state(qmps_ctx* c) {
 // at all) and none of their results; the fixed points of the last gradient batch stay where QMPS_BFGS_WARM looks for them (grad_warm_T)
 inline void forget_resident_candidates(qmps_ctx* c) {
   forget_resident_state(c);
-  c->n_states = 0; c->window = 0; c->tensors_valid = false;
-  c->ans_have = false; c->ans_src = nullptr; c->ans_i = nullptr; c->ans_nsh = 0;
+  c->states.hold_nothing();
+  c->window = 0;
 }
 // the window's slots of d_r as the start of a solve: only where something was put there
 inline bool window_has_start(const qmps_ctx* c, int64_t B) { return c->env_start.covers(c->window, c->window + B); }
 inline size_t tensor_bytes(const qmps_ctx* c) { return (size_t)32 * c->D * c->D; }
 inline size_t env_bytes(const qmps_ctx* c) { return (size_t)16 * c->D * c->D; }
-int ensure_scratch(qmps_ctx* c, size_t bytes);
-int ensure_E(qmps_ctx* c, int n_terms);
+// A device buffer that grows on demand and keeps no contents: room for `need` units of `cap` (whatever the buffer counts in), `bytes`
+// of HBM.  A failed allocation leaves no buffer AND no capacity, so the next call allocates again.  Nothing on the device may
+// still be using the old buffer.
+template <class T, class Cap>
+int grow(T*& buf, Cap& cap, Cap need, size_t bytes) {
+  if (need > cap) {
+    if (buf) HIP_TRY(hipFree(buf));
+    buf = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc((void**)&buf, bytes));
+    cap = need;
+  }
+  return QMPS_OK;
+}
+template <class T>
+int grow(T*& buf, size_t& have_bytes, size_t bytes) { return grow(buf, have_bytes, bytes, bytes); }      // (a buffer counted in bytes)
+inline int ensure_scratch(qmps_ctx* c, size_t bytes) { return grow(c->d_scratch, c->scratch_bytes, bytes); }
+inline int ensure_E(qmps_ctx* c, int n_terms) { return grow(c->d_E, c->E_capacity, c->max_batch * n_terms, (size_t)c->max_batch * n_terms * sizeof(double)); }
+// d_params: max_batch rows of n_params parameters
+inline int ensure_params(qmps_ctx* c, int n_params) { return grow(c->d_params, c->params_cap, n_params, (size_t)c->max_batch * n_params * sizeof(double)); }
 int check_B(const qmps_ctx* c, int64_t B);
 int check_window(const qmps_ctx* c, int64_t B);      // launch / read-back calls: the window [window, window + B) must lie inside the buffers
+int check_resident(const qmps_ctx* c, int64_t B);    // ... and inside the resident states
 // addresses of the window's first evaluation
 inline char* win_A(const qmps_ctx* c) { return (char*)c->d_A + (size_t)c->window * tensor_bytes(c); }
 inline char* win_r(const qmps_ctx* c) { return (char*)c->d_r + (size_t)c->window * env_bytes(c); }

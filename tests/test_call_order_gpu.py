@@ -656,3 +656,43 @@ def test_launches_over_the_same_states(D):
         assert np.abs(E1 - np.real(np.einsum('tij,bji->bt', I['h1'], rho))).max() < TE.E_TOL
         assert np.array_equal(it1, first[1]) and np.array_equal(st1, first[2])      # (the solve's own: the pass leaves them alone)
     print(f'same states D = {D}: 12 read-backs, {time.perf_counter() - t0:.2f} s')
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# qmps_get_states at B = 0: the one call whose answer tells "no states, tensors valid" from "nothing resident"
+
+
+def get_states(eng, B):
+    """(return code, message) of qmps_get_states(ctx, B, A)"""
+    A = np.empty((max(B, 1), 2, eng.D, eng.D), dtype=np.complex128)
+    rc = eng._lib.qmps_get_states(eng._ctx, B, C._f64(A.view(np.float64)))
+    return rc, (eng._lib.qmps_last_error().decode() if rc != L.QMPS_OK else '')
+
+
+@pytest.mark.parametrize('D', (2, 4))
+def test_get_states_of_an_empty_batch_tells_what_the_last_call_left(D):
+    """A fresh context, an upload and the two-site unit cell leave d_A readable (an empty read-back succeeds); the BFGS evolve drivers
+    leave nothing resident, and say so.  One state is more than a context without states holds, whoever emptied it."""
+    t0 = time.perf_counter()
+    I = C.inputs(D)
+    bfgs = dict(n_steps=1, maxiter=1)
+    histories = [('a fresh context', lambda eng: None, L.QMPS_OK, 0),
+                 ('qmps_set_states of 4 tensors', lambda eng: eng.set_tensors(I['A'][:4]), L.QMPS_OK, 4),
+                 ('qmps_evolve_bfgs', lambda eng: eng.evolve_bfgs(C.KIND, I['traj'][:2], I['WW'], counters=False, **bfgs), L.QMPS_ERR_STATE, 0),
+                 ('qmps_evolve_bfgs_device', lambda eng: eng.evolve_bfgs_device(C.KIND, I['traj'][:2], I['WW'], **bfgs), L.QMPS_ERR_STATE, 0)]
+    if D == 2:
+        histories.append(('the two-site unit cell', lambda eng: eng.cell2_energies(I['cell_U'][0][:4], I['cell_U'][1][:4], I['h']), L.QMPS_OK, 0))
+    for what, history, code, count in histories:
+        with EnergyEngine(D, 64) as eng:
+            history(eng)
+            rc, msg = get_states(eng, 0)
+            print(f'D = {D}, after {what}: qmps_get_states(0) -> {rc} {msg!r}')
+            assert rc == code, (what, rc, msg)
+            assert code == L.QMPS_OK or 'no resident states' in msg, (what, msg)
+            rc, msg = get_states(eng, 1)
+            print(f'D = {D}, after {what}: qmps_get_states(1) -> {rc} {msg!r}')
+            if count == 0:
+                assert rc == L.QMPS_ERR_STATE and 'only 0 states are resident' in msg, (what, rc, msg)
+            else:
+                assert rc == L.QMPS_OK, (what, rc, msg)
+    print(f'empty read-backs D = {D}: {len(histories)} histories, {time.perf_counter() - t0:.2f} s')

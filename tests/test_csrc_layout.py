@@ -89,3 +89,49 @@ def test_the_correlator_sum_dispatch_file_holds_no_kernels_and_no_kernel_asks_fo
     for f, text in src.items():
         for gone in ('Source::one_site', 'Source::two_site', 'if constexpr (SRC'):
             assert gone not in text, (f, gone)
+
+
+STATE_FIELDS = ('count', 'has_tensors', 'ansatz', 'kind', 'P', 'rows', 'shift_index', 'shifts')
+
+
+def test_the_resident_states_change_through_their_transitions_only():
+    """ResidentStates (qmps_resident.h) is assigned by its own member functions; everything else reads `states.<field>`.  The loose
+    fields it replaces are gone from the context and from the C-API files (LaneArgs, the launch argument of qmps_kernels.h, keeps
+    its ans_i and ans_nsh: in the C-API files the two names occur as members of a LaneArgs `a` only).  The search knows the spelling
+    `states.<field> =` alone: an assignment through a non-const reference to `states` would pass it, so the C-API takes none."""
+    src = sources()
+    header = src['qmps_resident.h']
+    for field in STATE_FIELDS:
+        assert re.search(r'\b%s\b' % field, header[header.index('struct ResidentStates'):]), field
+    assign = re.compile(r'states\.(%s)\s*=[^=]' % '|'.join(STATE_FIELDS))
+    for f, text in src.items():
+        if f != 'qmps_resident.h':
+            assert not assign.search(re.sub(r'//.*', '', text)), f
+    for f, text in src.items():
+        assert not re.search(r'(?<!const )ResidentStates\s*&', text), f
+    searched = {f: text for f, text in src.items() if f.startswith('qmps_capi') or f == 'qmps_ctx.h'}
+    assert len(searched) == 10, sorted(searched)
+    for f, text in searched.items():
+        for gone in ('ans_have', 'ans_src', 'tensors_valid', 'n_states'):
+            assert gone not in text, (f, gone)
+        for member in ('ans_i', 'ans_nsh'):
+            uses = re.findall(r'(.{2})\b%s\b' % member, text)
+            assert f != 'qmps_ctx.h' or not uses, (f, member)
+            assert all(u == 'a.' for u in uses), (f, member, uses)
+
+
+def test_device_buffers_are_freed_in_grow_and_at_the_end_only():
+    """hipFree in the C-API: inside grow() (qmps_ctx.h), in qmps_destroy, in the peak probes and for the tuning build's d_prof."""
+    src = sources()
+    ctx = src['qmps_ctx.h']
+    start = ctx.index('int grow(T*& buf, Cap& cap, Cap need, size_t bytes) {')
+    assert ctx.count('hipFree(') == 1 and start < ctx.index('hipFree(') < ctx.index('\n}\n', start)
+    capi = src['qmps_capi.hip']
+    start = capi.index('int qmps_destroy(qmps_ctx* c) try {')
+    end = capi.index('QMPS_API_CATCH', start)
+    assert 'hipFree(' not in capi[:start] + capi[end:] and 'hipFree(' in capi[start:end]
+    for f, text in src.items():
+        if f.startswith('qmps_capi') and f not in ('qmps_capi.hip', 'qmps_capi_probe.hip'):
+            frees = [line.strip() for line in text.splitlines() if 'hipFree(' in line]
+            assert frees == (['HIP_TRY(hipFree(d_prof));'] if f == 'qmps_capi_evolve.hip' else []), (f, frees)
+    assert sum(text.count('but only %lld states are resident') for text in src.values()) == 1
