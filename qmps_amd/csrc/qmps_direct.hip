@@ -15,6 +15,8 @@
 //      scalar loads
 //   -> E (8 B per term), iterations + status (8 B), optionally r (256 B); per-wave partial sums of E.
 // One read of A and one store of E per evaluation: the environment never travels through HBM.
+// The LDS operands of the matrix build, the cold start's acceptance step and its density phase are requested a block of arithmetic ahead of
+// their readers (QMPS_STAGE_FENCE and the operand sets of qmps_direct_core.h; tools/lds_cover.py lists every LDS wait with its cover).
 // The mathematics lives in qmps_direct_core.h (shared with the CPU lock-step emulation the test-suite uses).
 // Replaces qmps/tools.py:176-182 (get_env_exact: the reference does an exact eigen-solve here as well) +
 // qmps/represent.py:258-262 + qmps/ground_state.py:159-167.
@@ -309,15 +311,17 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
     Core::build(o, Rc);
     __builtin_amdgcn_sched_barrier(0);     // phase by phase: keeps the operand reads of later phases out of the register file
     double pivmax;
+    [[maybe_unused]] Core::Set8 own;      // cold start: the acceptance step's first operands, requested in front of the normalisation
     {
       double ur[16];
       Core::solve_gathered(o, Rc, ur, pivmax);
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (!WARM) Core::request_own_rows(o, own);
       Core::normalise_gathered(o, ur, us, xs);
     }
     double d2;
     if constexpr (WARM) d2 = Core::power_step(o, xs, us, y);
-    else d2 = Core::power_step_sites(o, xs, us, p.rho_need, y, W);
+    else d2 = Core::power_step_sites(o, own, xs, us, p.rho_need, y, W);
     __builtin_amdgcn_sched_barrier(0);
     const bool accepted = d2 < tol2 && pivmax < Core::kMaxInversePivot;     // NaN (a zero pivot) fails both
     if (!have) {
@@ -360,6 +364,11 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
   } else {
     Core::gather(x, us);
   }
+  // The shard count of the cost accumulation is in its scalar register HERE.  The compiler otherwise starts its load in front of the
+  // density phase, and a scalar load in flight - scalar loads return out of order - turns every counted wait for the staged LDS operands
+  // behind it into a wait for all of them (tools/lds_cover.py lists such a wait with the scalar load it retires).
+  int acc_shards = p.acc_shards;
+  asm volatile("" : "+s"(acc_shards));
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- positive definiteness, two-site density matrix, energies ----
@@ -379,7 +388,7 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
         // first pass of the cost reduction: one partial per wave, fixed order
         if (p.partial != nullptr) p.partial[(int64_t)t * gridDim.x + blockIdx.x] = s;
         // ... or the whole reduction: an exact fixed-point sum (order-independent) + the arrival count, ONE atomic
-        if (p.acc != nullptr) acc_arrive(p.acc, p.acc_shards, t, blockIdx.x, s, p.acc_bound, p.acc_scale);
+        if (p.acc != nullptr) acc_arrive(p.acc, acc_shards, t, blockIdx.x, s, p.acc_bound, p.acc_scale);
       }
     }
   }
@@ -408,12 +417,16 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
   }
   if (p.r_out != nullptr) {
     // row q of r: the lane owns u[(q,l)] = x[l]; the transposed coordinate u[(l,q)] comes out of the gathered copy
+    // (the own coordinates x are read back out of the gathered copy - the same bits on every path - so that x is not held through the
+    // density phase, whose staged operands need the registers)
     double2* o2 = (double2*)p.r_out + b * 16 + q * 4;
+    double xo[4];
+    Core::own_coords(o, us, xo);
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
       const double f = q == 0 ? us[4 * l] : (q == 1 ? us[4 * l + 1] : (q == 2 ? us[4 * l + 2] : us[4 * l + 3]));
-      const double re = q <= l ? x[l] : f;
-      const double im = q == l ? 0.0 : (q < l ? f : -x[l]);
+      const double re = q <= l ? xo[l] : f;
+      const double im = q == l ? 0.0 : (q < l ? f : -xo[l]);
       o2[l] = make_double2(re, im);
     }
   }

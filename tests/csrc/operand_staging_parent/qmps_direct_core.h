@@ -91,25 +91,8 @@ constexpr uint32_t rho_site_factors(uint32_t need) {
 // branch that first reads it and leaves the LDS reads behind it in flight - their data then fills the register file across the branches
 #if defined(__HIP_DEVICE_COMPILE__)
 #define QMPS_COMPUTED_HERE(v) asm volatile("" : "+v"(v))
-#define QMPS_COMPUTED_HERE8(a, b, c, d, e, f, g, h) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h))
 #else
 #define QMPS_COMPUTED_HERE(v) ((void)0)
-#define QMPS_COMPUTED_HERE8(a, b, c, d, e, f, g, h) ((void)0)
-#endif
-// Operand staging: the tensor entries of a block of arithmetic (one partner index of build, own_rows_times_r, half a site_w, half an N
-// factor) are REQUESTED - plain reads through the accessors into a named operand set - one block ahead:
-//     request(set of block n + 1);  QMPS_STAGE_FENCE();  needed_here(set of block n);  arithmetic of block n
-// The fence keeps the requests in front of the arithmetic of the block before, needed_here makes the set of block n one wait; left to itself
-// the compiler puts every read directly in front of its reader and the wave stops for the LDS dozens of times.  A fence INSIDE a phase: it
-// writes a mark into the text, by which tools/isa_mix.py tells it from the fences between phases.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define QMPS_STAGE_FENCE()                   \
-  do {                                       \
-    asm volatile("; qmps_stage_fence");      \
-    __builtin_amdgcn_sched_barrier(0);       \
-  } while (0)
-#else
-#define QMPS_STAGE_FENCE() ((void)0)
 #endif
 
 template <int... I, class F>
@@ -131,84 +114,20 @@ struct DirectD4 {
     return O::sel(o.q_eq(0), x[0], O::sel(o.q_eq(1), x[1], O::sel(o.q_eq(2), x[2], x[3])));
   }
 
-  // ---- operand sets (QMPS_STAGE_FENCE): eight or four complex tensor entries in registers ----
-  struct Set8 {
-    V re[2][4], im[2][4];
-  };
-  struct Set4 {
-    V re[4], im[4];
-  };
-  // (one statement for the set: one wait for all of its reads, where a statement per value waits for them one by one)
-  static QMPS_CORE_FN void needed_here(Set8& a) {
-    QMPS_COMPUTED_HERE8(a.re[0][0], a.re[0][1], a.re[0][2], a.re[0][3], a.re[1][0], a.re[1][1], a.re[1][2], a.re[1][3]);
-    QMPS_COMPUTED_HERE8(a.im[0][0], a.im[0][1], a.im[0][2], a.im[0][3], a.im[1][0], a.im[1][1], a.im[1][2], a.im[1][3]);
-  }
-  static QMPS_CORE_FN void needed_here(Set4& a) {
-    QMPS_COMPUTED_HERE8(a.re[0], a.re[1], a.re[2], a.re[3], a.im[0], a.im[1], a.im[2], a.im[3]);
-  }
-  // the results of a block: computed in front of the next fence, not sunk into a branch behind it
-  static QMPS_CORE_FN void computed_here(V (&a)[4], V (&b)[4]) {
-    QMPS_COMPUTED_HERE8(a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]);
-  }
-  static QMPS_CORE_FN void half_computed(V (&a)[4], V (&b)[4], int half) {
-    QMPS_COMPUTED_HERE(a[2 * half]);
-    QMPS_COMPUTED_HERE(a[2 * half + 1]);
-    QMPS_COMPUTED_HERE(b[2 * half]);
-    QMPS_COMPUTED_HERE(b[2 * half + 1]);
-  }
-  // the lane's own rows: [s][j] = A_s[q][j]  (build, own_rows_times_r)
-  static QMPS_CORE_FN void request_own_rows(const O& o, Set8& a) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o.own(s, j, a.re[s][j], a.im[s][j]);
-  }
-  // the rows of partner index ip: [s][j] = A_s[ip][j]  (a block of build)
-  static QMPS_CORE_FN void request_partner_rows(const O& o, int ip, Set8& b) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o.uni(s, ip, j, b.re[s][j], b.im[s][j]);
-  }
-  // two rows of A_s: [i][k] = A_s[2 half + i][k]  (half a site_w)
-  static QMPS_CORE_FN void request_row_pair(const O& o, int s, int half, Set8& b) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o.uni(s, 2 * half + i, k, b.re[i][k], b.im[i][k]);
-  }
-  // two columns of A_s: [l][i] = A_s[i][2 half + l]  (half an N factor of density_sites)
-  static QMPS_CORE_FN void request_col_pair(const O& o, int s, int half, Set8& b) {
-#pragma unroll
-    for (int l = 0; l < 2; ++l)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) o.uni(s, i, 2 * half + l, b.re[l][i], b.im[l][i]);
-  }
-  // the lane's own column: [i] = A_s[i][q]
-  static QMPS_CORE_FN void request_own_col(const O& o, int s, Set4& c) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o.col(s, i, c.re[i], c.im[i]);
-  }
-
   // ---- 1. the lane's four rows of the real transfer matrix: Rc[i'][4 j + j'] = coordinate (q, i') of T(H_(j,j')) ----
   // With P(j,j') = sum_s (gamma A_s[q][j]) conj(A_s[i'][j']), gamma = 1 (q <= i': a real part) or i (q > i': minus an
   // imaginary part):  column (j,j): Re P(j,j);  column (lo,hi): Re (P(lo,hi) + P(hi,lo));
   // column (hi,lo): -Im (P(lo,hi) - P(hi,lo)).
-  // A block is one partner index (100 multiply-adds); its partner rows are requested a block ahead.
   static QMPS_CORE_FN void build(const O& o, V (&Rc)[4][16]) {
-    Set8 own, partner[4];
-    request_own_rows(o, own);
-    request_partner_rows(o, 0, partner[0]);
-    const V(&ar)[2][4] = own.re, (&ai)[2][4] = own.im;
+    V ar[2][4], ai[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o.own(s, j, ar[s][j], ai[s][j]);
 #pragma unroll
     for (int ip = 0; ip < 4; ++ip) {
-      if (ip < 3) request_partner_rows(o, ip + 1, partner[ip + 1]);
-      QMPS_STAGE_FENCE();
-      if (ip == 0) needed_here(own);
-      needed_here(partner[ip]);
-      const V(&br)[2][4] = partner[ip].re, (&bi)[2][4] = partner[ip].im;
       const P rot = o.q_gt(ip);
-      V tr[2][4], ti[2][4];
+      V tr[2][4], ti[2][4], br[2][4], bi[2][4];
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -216,6 +135,7 @@ struct DirectD4 {
           // (no lane has q > 3: the last partner index needs no select)
           tr[s][j] = ip == 3 ? ar[s][j] : O::sel(rot, -ai[s][j], ar[s][j]);
           ti[s][j] = ip == 3 ? ai[s][j] : O::sel(rot, ar[s][j], ai[s][j]);
+          o.uni(s, ip, j, br[s][j], bi[s][j]);
         }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -408,12 +328,11 @@ struct DirectD4 {
   }
   // X_s = A_s[q][:] r, s = 0, 1
   static QMPS_CORE_FN void own_rows_times_r(const O& o, const V (&us)[16], V (&xr)[2][4], V (&xi)[2][4]) {
-    Set8 own;
-    request_own_rows(o, own);
-    own_rows_times_r(own.re, own.im, us, xr, xi);
-  }
-  // ... from the own rows in registers (request_own_rows)
-  static QMPS_CORE_FN void own_rows_times_r(const V (&ar)[2][4], const V (&ai)[2][4], const V (&us)[16], V (&xr)[2][4], V (&xi)[2][4]) {
+    V ar[2][4], ai[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o.own(s, j, ar[s][j], ai[s][j]);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -444,92 +363,38 @@ struct DirectD4 {
   // y = (W_00 + W_11)/tr and the distance to x, as power_step (another summation order: the halves are summed apart).  w: W_00 and W_11, and
   // whichever of W_01, W_10 the mask reads (rho_site_factors(need); wave-uniform tests) - the other one is NOT written.
   static QMPS_CORE_FN V power_step_sites(const O& o, const V (&x)[4], const V (&us)[16], uint32_t need, V (&y)[4], SiteW& w) {
-    Set8 own;
-    request_own_rows(o, own);
-    return power_step_sites(o, own, x, us, need, y, w);
-  }
-  // ... with its operands staged (QMPS_STAGE_FENCE).  own: the lane's own rows, requested by the caller a block of arithmetic earlier
-  // (request_own_rows).  The blocks: own_rows_times_r, then each W in two halves of two rows of A_s2; two row pairs are live at a time.
-  static QMPS_CORE_FN V power_step_sites(const O& o, Set8& own, const V (&x)[4], const V (&us)[16], uint32_t need, V (&y)[4], SiteW& w) {
-    const uint32_t f = rho_site_factors(need);
     V xr[2][4], xi[2][4];
-    Set8 a, b;
-    request_row_pair(o, 0, 0, a);
-    QMPS_STAGE_FENCE();
-    needed_here(own);
-    own_rows_times_r(own.re, own.im, us, xr, xi);
-    computed_here(xr[0], xi[0]);
-    computed_here(xr[1], xi[1]);
-    request_row_pair(o, 0, 1, b);
-    QMPS_STAGE_FENCE();
-    needed_here(a);
-    site_w_half(xr[0], xi[0], a, 0, w.re[0][0], w.im[0][0]);
-    half_computed(w.re[0][0], w.im[0][0], 0);
-    request_row_pair(o, 1, 0, a);
-    QMPS_STAGE_FENCE();
-    needed_here(b);
-    site_w_half(xr[0], xi[0], b, 1, w.re[0][0], w.im[0][0]);
-    half_computed(w.re[0][0], w.im[0][0], 1);
-    request_row_pair(o, 1, 1, b);
-    QMPS_STAGE_FENCE();
-    needed_here(a);
-    site_w_half(xr[1], xi[1], a, 0, w.re[1][1], w.im[1][1]);
-    half_computed(w.re[1][1], w.im[1][1], 0);
-    QMPS_STAGE_FENCE();
-    needed_here(b);
-    site_w_half(xr[1], xi[1], b, 1, w.re[1][1], w.im[1][1]);
-    half_computed(w.re[1][1], w.im[1][1], 1);
+    own_rows_times_r(o, us, xr, xi);
+    site_w(o, xr[0], xi[0], 0, w.re[0][0], w.im[0][0]);
+    site_w(o, xr[1], xi[1], 1, w.re[1][1], w.im[1][1]);
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
       const V cr = w.re[0][0][l] + w.re[1][1][l];
       y[l] = l == 3 ? cr : O::sel(o.q_gt(l), -(w.im[0][0][l] + w.im[1][1][l]), cr);
     }
-    // (the same two tests of the mask as before the staging, wave-uniform)
-    if (f & kSiteW01) {
-      // W_01 reads the rows of A_1 as W_11 did: both pairs are still in registers
-      site_w_half(xr[0], xi[0], a, 0, w.re[0][1], w.im[0][1]);
-      site_w_half(xr[0], xi[0], b, 1, w.re[0][1], w.im[0][1]);
-      computed_here(w.re[0][1], w.im[0][1]);
-    }
-    if (f & kSiteW10) {
-      // W_10 reads the rows of A_0 again: both pairs requested here, the second one behind the first one's arithmetic
-      request_row_pair(o, 0, 0, a);
-      request_row_pair(o, 0, 1, b);
-      QMPS_STAGE_FENCE();
-      needed_here(a);
-      site_w_half(xr[1], xi[1], a, 0, w.re[1][0], w.im[1][0]);
-      half_computed(w.re[1][0], w.im[1][0], 0);
-      QMPS_STAGE_FENCE();
-      needed_here(b);
-      site_w_half(xr[1], xi[1], b, 1, w.re[1][0], w.im[1][0]);
-      half_computed(w.re[1][0], w.im[1][0], 1);
-    }
+    const uint32_t f = rho_site_factors(need);
+    if (f & kSiteW01) site_w(o, xr[0], xi[0], 1, w.re[0][1], w.im[0][1]);
+    if (f & kSiteW10) site_w(o, xr[1], xi[1], 0, w.re[1][0], w.im[1][0]);
     normalise(o, y);
     return dist2(o, x, y);
-  }
-  // two of the four entries of site_w from their rows of A_s2 in registers (request_row_pair): l = 2 half, 2 half + 1
-  static QMPS_CORE_FN void site_w_half(const V (&xr)[4], const V (&xi)[4], const Set8& rows, int half, V (&wre)[4], V (&wim)[4]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      V cr = O::fma(xi[0], rows.im[i][0], xr[0] * rows.re[i][0]), ci = O::fma(-xr[0], rows.im[i][0], xi[0] * rows.re[i][0]);
-#pragma unroll
-      for (int k = 1; k < 4; ++k) {
-        cr = O::fma(xr[k], rows.re[i][k], cr);
-        cr = O::fma(xi[k], rows.im[i][k], cr);
-        ci = O::fma(xi[k], rows.re[i][k], ci);
-        ci = O::fma(-xr[k], rows.im[i][k], ci);
-      }
-      wre[2 * half + i] = cr;
-      wim[2 * half + i] = ci;
-    }
   }
   // (X A_s2^+)[l] = sum_k X[k] conj(A_s2[l][k])
   static QMPS_CORE_FN void site_w(const O& o, const V (&xr)[4], const V (&xi)[4], int s2, V (&wre)[4], V (&wim)[4]) {
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      Set8 rows;
-      request_row_pair(o, s2, half, rows);
-      site_w_half(xr, xi, rows, half, wre, wim);
+    for (int l = 0; l < 4; ++l) {
+      V br, bi;
+      o.uni(s2, l, 0, br, bi);
+      V cr = O::fma(xi[0], bi, xr[0] * br), ci = O::fma(-xr[0], bi, xi[0] * br);
+#pragma unroll
+      for (int k = 1; k < 4; ++k) {
+        o.uni(s2, l, k, br, bi);
+        cr = O::fma(xr[k], br, cr);
+        cr = O::fma(xi[k], bi, cr);
+        ci = O::fma(xi[k], br, ci);
+        ci = O::fma(-xr[k], bi, ci);
+      }
+      wre[l] = cr;
+      wim[l] = ci;
     }
   }
   // The W of another r (us) for the evaluations p; the others keep theirs, bit for bit - an evaluation whose environment changed after the
@@ -868,22 +733,10 @@ struct DirectD4 {
   // an r that fails the pivot test needs no route of its own.  One N is live at a time; a part the mask leaves out is exactly 0.0, and a
   // part that is computed sees the same operations in the same order whatever the mask.
   static QMPS_CORE_FN P density_sites(const O& o, const V (&us)[16], uint32_t need, const SiteW& w, V (&pre)[4][4], V (&pim)[4][4]) {
-    // Operands staged (QMPS_STAGE_FENCE): an N factor in two halves of two columns of A_s1, two column pairs live at a time; the first pair
-    // is requested in front of the LDL^H test.  The requests do not ask the mask (a factor it leaves out is a rare Hamiltonian; its reads
-    // are in bounds and cost no arithmetic).  Column q of A_0 serves N_00 and N_10, the columns of A_1 serve N_10 and N_11 from the same
-    // registers: 40 reads.
-    Set4 own_col[2];
-    Set8 cols[2];
-    request_own_col(o, 0, own_col[0]);
-    request_col_pair(o, 0, 0, cols[0]);
-    QMPS_STAGE_FENCE();
     P pd;
     {
       V rre[4][4], rim[4][4], lre[4][4], lim[4][4], d[4];
       pd = ldl(us, rre, rim, lre, lim, d);
-      // (the pivots exist here, behind the first requests: only the status reads the test, and the compiler would move it down there)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) QMPS_COMPUTED_HERE(d[j]);
     }
 #pragma unroll
     for (int tau = 0; tau < 4; ++tau)
@@ -893,40 +746,29 @@ struct DirectD4 {
         pim[tau][sg] = O::splat(0.0);
       }
     static_for<3>([&](auto F) {
-      constexpr int fi = decltype(F)::value, s1 = fi == 0 ? 0 : 1, t1 = fi == 2 ? 1 : 0;
-      constexpr uint32_t parts = rho_site_parts(1u << fi);      // kSiteN00, kSiteN10, kSiteN11
-      // column q of N_{s1 t1}: N[l][q] = sum_i conj(A_s1[i][l]) A_t1[i][q]
-      V nre[4], nim[4];
-      static_for<2>([&](auto H) {
-        constexpr int half = decltype(H)::value;
-        // the next half's column pair - behind the second half the next factor's first, or for N_11, which reads the columns of A_1 as
-        // N_10 did (both pairs are still in registers), its own column alone
-        if (half == 0 && fi < 2) request_col_pair(o, s1, 1, cols[1]);
-        if (half == 1 && fi == 0) request_col_pair(o, 1, 0, cols[0]);
-        if (half == 1 && fi == 1) request_own_col(o, 1, own_col[1]);
-        QMPS_STAGE_FENCE();
-        if (need & parts) {
-          if (half == 0 && fi != 1) needed_here(own_col[t1]);
-          needed_here(cols[half]);
-          const V(&cr)[4] = own_col[t1].re, (&ci)[4] = own_col[t1].im;
-#pragma unroll
-          for (int l = 0; l < 2; ++l) {
-            const V(&ur)[4] = cols[half].re[l], (&ui)[4] = cols[half].im[l];
-            V re = O::fma(ui[0], ci[0], ur[0] * cr[0]), im = O::fma(-ui[0], cr[0], ur[0] * ci[0]);
-#pragma unroll
-            for (int i = 1; i < 4; ++i) {
-              re = O::fma(ur[i], cr[i], re);
-              re = O::fma(ui[i], ci[i], re);
-              im = O::fma(ur[i], ci[i], im);
-              im = O::fma(-ui[i], cr[i], im);
-            }
-            nre[2 * half + l] = re;
-            nim[2 * half + l] = im;
-          }
-          half_computed(nre, nim, half);
-        }
-      });
+      constexpr int s1 = decltype(F)::value == 0 ? 0 : 1, t1 = decltype(F)::value == 2 ? 1 : 0;
+      constexpr uint32_t parts = rho_site_parts(1u << decltype(F)::value);      // kSiteN00, kSiteN10, kSiteN11
       if (need & parts) {
+        // column q of N_{s1 t1}: N[l][q] = sum_i conj(A_s1[i][l]) A_t1[i][q]
+        V cr[4], ci[4], nre[4], nim[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o.col(t1, i, cr[i], ci[i]);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+          V ur, ui;
+          o.uni(s1, 0, l, ur, ui);
+          V re = O::fma(ui, ci[0], ur * cr[0]), im = O::fma(-ui, cr[0], ur * ci[0]);
+#pragma unroll
+          for (int i = 1; i < 4; ++i) {
+            o.uni(s1, i, l, ur, ui);
+            re = O::fma(ur, cr[i], re);
+            re = O::fma(ui, ci[i], re);
+            im = O::fma(ur, ci[i], im);
+            im = O::fma(-ui, cr[i], im);
+          }
+          nre[l] = re;
+          nim[l] = im;
+        }
 #pragma unroll
         for (int l = 0; l < 4; ++l) {       // (the tests of the parts follow)
           QMPS_COMPUTED_HERE(nre[l]);

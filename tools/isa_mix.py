@@ -11,6 +11,8 @@ Counts are static (one pass over the text); the rare phases (the fall-back with 
 sources the density of an r that is not positive definite) are code that the common path branches over, and "common path" is
 the total without them.  The compiler moves arithmetic whose result is read late (the LDL^H pivots: only the status reads them)
 down to its reader, across the fences: compare totals rather than single phases.
+The staging fences inside a phase (QMPS_STAGE_FENCE: a sched_barrier behind a mark in the text) are no phase boundaries; tools/lds_cover.py
+reads the same phases for the LDS waits.
 --all lists the register and scratch use of every energy_direct_d4_kernel / energy_only_d4_kernel instantiation.
 """
 import argparse
@@ -32,6 +34,7 @@ PHASES_LDL = ['load+build', 'solve', 'accept', 'fallback', 'density', 'density n
 PHASES_OLD = ['load+build', 'solve', 'accept', 'fallback', 'density+energy']
 RARE = ['fallback', 'density not-PD']     # branches the common path skips
 FENCE = re.compile(r';\s*sched_barrier mask\(0x0+\)')
+STAGE_MARK = 'qmps_stage_fence'
 COLS = ['f64', 'dpp', 'cndmask', 'ds_read', 's_nop', 'valu']
 
 
@@ -73,11 +76,31 @@ def classify(op):
     return out
 
 
+def is_phase_fence(text, n):
+    """line n is a fence between two phases: a sched_barrier that is not a staging fence (QMPS_STAGE_FENCE of qmps_direct_core.h, which
+    writes STAGE_MARK into the text in front of its sched_barrier: a fence inside a phase, between a block's requests and arithmetic)"""
+    if not FENCE.match(text[n].strip()):
+        return False
+    # (the mark and its sched_barrier keep their order - both have side effects - but other instructions may stand between them: the
+    # nearest fence or mark above decides)
+    for back in range(n - 1, -1, -1):
+        s = text[back].strip()
+        if STAGE_MARK in s:
+            return False
+        if FENCE.match(s):
+            break
+    return True
+
+
+def phase_names(n_phases):
+    return next((n for n in (PHASES, PHASES_LDL, PHASES_OLD) if len(n) == n_phases), [f'phase {i}' for i in range(n_phases)])
+
+
 def mix(text):
     phases = [collections.Counter()]
-    for ln in text:
+    for n, ln in enumerate(text):
         s = ln.strip()
-        if FENCE.match(s):
+        if is_phase_fence(text, n):
             phases.append(collections.Counter())
             continue
         if not s or s.startswith((';', '.')) or s.endswith(':'):
@@ -98,7 +121,7 @@ def main():
         lines = open(path).read().split('\n')
     text, res = body(lines, a.kernel)
     phases = mix(text)
-    names = next((n for n in (PHASES, PHASES_LDL, PHASES_OLD) if len(n) == len(phases)), [f'phase {i}' for i in range(len(phases))])
+    names = phase_names(len(phases))
     print(f'{a.kernel}')
     print(f'{"phase":<16}' + ''.join(f'{c:>9}' for c in COLS))
     tot = collections.Counter()
