@@ -199,6 +199,8 @@ int qmps_abi_version(void);
  *      qmps_entanglement, their Schmidt spectra and entanglement entropies; qmps_correlator_sums, the sums over all distances of their
  *      connected two-point functions (structure factors).
  *      qmps_correlator_sums_two_site, the same sums for two-site operators (energy-density structure factors, the energy variance per site).
+ *      qmps_string_correlators, the two-point functions with a one-site string between their ends and the string order itself (disorder
+ *      parameters, Jordan-Wigner fermion functions).
  *      Changed later without a bump (same signatures; nothing a caller can detect beforehand, a refusal is an error code):
  *      RESIDENT RESULTS (below): the context knows per evaluation slot, not per context, what its buffers hold, and read-backs that used to return
  *      whatever the buffer held now fail with QMPS_ERR_STATE (same signatures).  qmps_get_env, qmps_get_rdm, qmps_energy_only_launch, qmps_correlators,
@@ -407,6 +409,31 @@ int qmps_get_rdm(qmps_ctx* ctx, int64_t B, double* rho);
 int qmps_correlators(qmps_ctx* ctx, int64_t B, int n_ops, const double* ops /* [n_ops][2][2] complex128 */, int n_max,
                      double* C_out   /* [B][n_ops][n_ops][n_max] complex128 */,
                      double* one_out /* nullable, [B][n_ops] complex128 */);
+/* String order of the resident states [window, window + B) with their resident environments (nothing is solved): the two-point
+ * functions of qmps_correlators with a one-site operator S - the string, S[t][s] = <t|S|s>, 2 x 2 complex, any matrix - on every site
+ * between their ends, and the expectation of the string alone.  With E_O, O[t][s] as in qmps_correlators, tau = tr r,
+ * L_a = sum_(t,s) O_a[t][s] A_t^+ A_s (so that tr(E_(O_a)(x)) = tr(L_a x)) and E_S(x) = sum_(t,s) S[t][s] A_s x A_t^+ in the place of T:
+ *   C_out[b][a][c][n-1] = tr(L_a E_S^(n-1)(E_(O_c)(r))) / tau = <O_a(site 0) S(1) ... S(n-1) O_c(site n)>,  n = 1 .. n_max
+ *   str_out[b][n-1]     = tr(E_S^n(r)) / tau                  = <S(1) ... S(n)>,                          n = 1 .. n_max
+ *   one_out[b][a]       = tr(L_a r) / tau                     = <O_a>                                     (as in qmps_correlators)
+ * C at n = 1 holds no string site and equals that of qmps_correlators; S = 1 gives qmps_correlators throughout and str = 1.  With
+ * S = X: str is the disorder parameter <X_1 .. X_n> of the transverse-field Ising chain, and the Jordan-Wigner fermion function
+ * <c^+_0 c_n> is a combination of the C of O = Z, Y.  The left environment is taken to be the identity, as in qmps_get_rdm and
+ * qmps_correlators: for tensors that are not left isometries the formulas above are still what is computed (site 0 is then the first
+ * site that carries an operator; everything to its left is traced with the identity).
+ * The contract is that of qmps_correlators word for word - argument checks before anything else, the window, QMPS_ERR_STATE without a
+ * resident environment, NaN for an evaluation whose tr r is zero or not finite, one upload, one kernel launch and one synchronisation,
+ * nothing resident changes, a refused call writes and allocates nothing, B = 0 writes nothing - with these limits: 1 <= n_ops <= 4,
+ * 1 <= n_max <= 4096, string not NULL (QMPS_ERR_ARG), and the results, B * (n_ops^2 + 1) * n_max * 16 bytes when str_out is given and
+ * B * n_ops^2 * n_max * 16 bytes when it is NULL, may not exceed 1 GiB.  one_out and str_out may be NULL.
+ * Sums over all distances are not offered: they are the resolvent of E_S, whose spectrum touches the unit circle on states symmetric
+ * under S (there str does not decay).  Cost: that of qmps_correlators plus the mixing of the four weights into every step and, with
+ * str_out, one more chain. */
+int qmps_string_correlators(qmps_ctx* ctx, int64_t B, int n_ops, const double* ops /* [n_ops][2][2] complex128 */,
+                            const double* string /* [2][2] complex128 */, int n_max,
+                            double* C_out   /* [B][n_ops][n_ops][n_max] complex128 */,
+                            double* one_out /* nullable, [B][n_ops] complex128 */,
+                            double* str_out /* nullable, [B][n_max] complex128 */);
 /* Entanglement (Schmidt) spectrum of the resident states [window, window + B) from their resident environments (nothing is solved):
  *   p_out[b][k]    = k-th largest eigenvalue of herm(r_b) / tr r_b, k = 0 .. D-1 (descending; signed: an environment that is
  *                    not positive definite shows its negative eigenvalues),  herm(r) = (r + r^+) / 2

@@ -1,4 +1,4 @@
-// qmps_capi_observables.hip - C-ABI of the observables of the resident states: two-point functions (kernels: qmps_correlator.hip),
+// qmps_capi_observables.hip - C-ABI of the observables of the resident states: two-point functions and string order (kernels: qmps_correlator.hip),
 // Schmidt spectra and entropies (qmps_entanglement.hip), correlator sums of one-site and of two-site operators (qmps_corrsum.hip and the kernel files it dispatches to).  Every call checks its own arguments,
 // passes the shared front, carves its regions out of the scratch buffer, uploads its inputs, launches ONE kernel, reads its results
 // back and synchronises ONE time.  A refused call writes nothing and allocates nothing.
@@ -112,29 +112,41 @@ int correlator_sums_call(qmps_ctx* c, int64_t B, int n_ops, const double* ops, i
   return QMPS_OK;
 }
 
-
-}  // namespace
-
-extern "C" {
-
-int qmps_correlators(qmps_ctx* c, int64_t B, int n_ops, const double* ops, int n_max, double* C_out, double* one_out) try {
+// qmps_correlators and qmps_string_correlators: one contract, one body.  `with_string`: the string call, whose `string` must not be
+// null; it uploads the string behind the operators (still one upload), launches the kernels of the string chain and may return str.
+int correlators_call(qmps_ctx* c, int64_t B, int n_ops, const double* ops, bool with_string, const double* string, int n_max, double* C_out,
+                     double* one_out, double* str_out) {
   if (!c) return fail(QMPS_ERR_ARG, "null context");
   if (!ops) return fail(QMPS_ERR_ARG, "null ops");
+  if (with_string && !string) return fail(QMPS_ERR_ARG, "null string");
   if (!C_out) return fail(QMPS_ERR_ARG, "null C_out");
   if (int rc = check_n_ops(n_ops)) return rc;
   if (n_max < 1 || n_max > 4096) return fail(QMPS_ERR_ARG, "n_max=%d outside [1, 4096]", n_max);
-  const uint64_t per_eval = (uint64_t)n_ops * n_ops * n_max * 16;
+  const uint64_t per_eval = ((uint64_t)n_ops * n_ops + (str_out ? 1 : 0)) * n_max * 16;
   bool empty = false;
   if (int rc = resident_front(c, B, per_eval, "n_max", empty)) return rc;
   if (empty) return QMPS_OK;
   if (int rc = ensure_tensors(c)) return rc;
-  const size_t C_bytes = (size_t)B * per_eval, one_bytes = (size_t)B * n_ops * 16;
+  const size_t op_bytes = qmps::kOneSiteOpBytes, ops_bytes = (size_t)n_ops * op_bytes;
+  const size_t C_bytes = (size_t)B * n_ops * n_ops * n_max * 16, one_bytes = (size_t)B * n_ops * 16, str_bytes = str_out ? (size_t)B * n_max * 16 : 0;
   ScratchLayout s;
-  const size_t ops_at = s.take(qmps::kMaxObservableOps * qmps::kOneSiteOpBytes), C_at = s.take(C_bytes), one_at = s.take(one_bytes);
+  const size_t ops_at = s.take((qmps::kMaxObservableOps + 1) * op_bytes);
+  s.align(256);      // the runs of the kernels' stores stay whole cache lines
+  const size_t C_at = s.take(C_bytes), one_at = s.take(one_bytes), str_at = s.take(str_bytes);
   if (int rc = ensure_scratch(c, s.bytes)) return rc;
   char* base = (char*)c->d_scratch;
-  char *d_ops = base + ops_at, *d_C = base + C_at, *d_one = base + one_at;
-  HIP_TRY(hipMemcpyAsync(d_ops, ops, (size_t)n_ops * qmps::kOneSiteOpBytes, hipMemcpyHostToDevice, c->stream));
+  char *d_ops = base + ops_at, *d_C = base + C_at, *d_one = base + one_at, *d_str = base + str_at;
+  // the string travels behind the operators: one upload either way (the staging copy lives until the synchronisation below)
+  double staged[(qmps::kMaxObservableOps + 1) * (qmps::kOneSiteOpBytes / sizeof(double))];
+  const double* src = ops;
+  size_t up_bytes = ops_bytes;
+  if (with_string) {
+    memcpy(staged, ops, ops_bytes);
+    memcpy((char*)staged + ops_bytes, string, op_bytes);
+    src = staged;
+    up_bytes += op_bytes;
+  }
+  HIP_TRY(hipMemcpyAsync(d_ops, src, up_bytes, hipMemcpyHostToDevice, c->stream));
   qmps::CorrelatorArgs a{};
   a.A = win_A(c);
   a.r = win_r(c);
@@ -144,11 +156,30 @@ int qmps_correlators(qmps_ctx* c, int64_t B, int n_ops, const double* ops, int n
   a.B = B;
   a.n_ops = n_ops;
   a.n_max = n_max;
-  if (int rc = timed_launch(c, "correlator", qmps::launch_correlators, a)) return rc;
+  a.string = with_string ? d_ops + ops_bytes : nullptr;
+  a.str = str_out ? d_str : nullptr;
+  if (int rc = with_string ? timed_launch(c, "string_correlator", qmps::launch_string_correlators, a)
+                           : timed_launch(c, "correlator", qmps::launch_correlators, a))
+    return rc;
   HIP_TRY(hipMemcpyAsync(C_out, d_C, C_bytes, hipMemcpyDeviceToHost, c->stream));
   if (one_out) HIP_TRY(hipMemcpyAsync(one_out, d_one, one_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (str_out) HIP_TRY(hipMemcpyAsync(str_out, d_str, str_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return QMPS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmps_correlators(qmps_ctx* c, int64_t B, int n_ops, const double* ops, int n_max, double* C_out, double* one_out) try {
+  return correlators_call(c, B, n_ops, ops, false, nullptr, n_max, C_out, one_out, nullptr);
+}
+QMPS_API_CATCH
+
+int qmps_string_correlators(qmps_ctx* c, int64_t B, int n_ops, const double* ops, const double* string, int n_max, double* C_out,
+                            double* one_out, double* str_out) try {
+  return correlators_call(c, B, n_ops, ops, true, string, n_max, C_out, one_out, str_out);
 }
 QMPS_API_CATCH
 

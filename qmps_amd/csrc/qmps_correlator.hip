@@ -5,6 +5,11 @@
 // registers (D = 2, 4) or LDS (D = 8, 16) for the whole chain, the chains of the n_ops right operators run one after the other.
 // Every loop has a fixed trip count (n_ops, n_max); there are no atomics, counters or waits between workgroups.
 // Results leave through an LDS tile of a few steps, so that the stores are contiguous runs along n.
+// String order (qmps_string_correlators): the same kernels instantiated with another chain type.  With a one-site string S the step
+// of every chain is E_S in the place of T,
+//   C[a][c][n-1] = tr(L_a E_S^(n-1)(x_c)) / tr r = <O_a(0) S(1) .. S(n-1) O_c(n)>,   str[n-1] = tr(E_S^n(r)) / tr r = <S(1) .. S(n)>,
+// which costs the mixing of the weights S[t][s] into every step; str is one more chain from r, read out by the plain trace.
+// The chain is a type (PlainChain, StringChain): an instantiation holds one kind of step, and the plain one does what it always did.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,9 +36,62 @@ __device__ __forceinline__ double group_sum(double v) {
   else return v + quad_perm<0xB1>(v);
 }
 
+// a b with the FMA order written out: the second product of the real part and the first of the imaginary part are rounded on their
+// own.  (cmul leaves to the compiler which product of each part is fused; these are the bits qmps_correlators has always returned.)
+__device__ __forceinline__ double2 cmul_rows(const double2 a, const double2 b) {
+  return make_double2(dfma(a.x, b.x, -(a.y * b.y)), dfma(a.y, b.x, a.x * b.y));
+}
+// z_s = sum_t W[t][s] y_t: the weights of E_W between the right and the left multiplication of the row kernels
+template <int D>
+__device__ __forceinline__ void mix_rows(const double2 w00, const double2 w01, const double2 w10, const double2 w11, const double2 (&y)[2][D],
+                                         double2 (&z)[2][D]) {
+#pragma unroll
+  for (int l = 0; l < D; ++l) {
+    z[0][l] = cmul_rows(w00, y[0][l]);
+    cfma(w10, y[1][l], z[0][l]);
+    z[1][l] = cmul_rows(w01, y[0][l]);
+    cfma(w11, y[1][l], z[1][l]);
+  }
+}
+
+// ---- the chain: what one step x -> E(x) of a chain puts between its two multiplications ---------------------------------------
+// A kernel is instantiated with one of the two types, so the n loop of an instantiation holds one kind of step and no test.
+// `mixed` (row kernels): the y_t the left multiplication takes; `step` (block kernels): the call of `apply` for the x in LDS.
+struct PlainChain {        // T = E_1: the y_t go on as they are
+  static constexpr bool kString = false;
+  __device__ explicit PlainChain(const CorrelatorArgs&) {}
+  __device__ __forceinline__ int n_chains(const CorrelatorArgs& p) const { return p.n_ops; }
+  template <int D>
+  __device__ __forceinline__ const double2 (&mixed(const double2 (&y)[2][D], double2 (&)[2][D]) const)[2][D] {
+    return y;
+  }
+  template <class Apply>
+  __device__ __forceinline__ double2 step(Apply&& apply) const {
+    const double2 zero = make_double2(0.0, 0.0);
+    return apply(zero, zero, zero, zero, true);
+  }
+};
+struct StringChain {       // E_S: the four entries of S, uniform, live in scalar registers for the whole kernel
+  static constexpr bool kString = true;
+  double2 w00, w01, w10, w11;
+  __device__ explicit StringChain(const CorrelatorArgs& p)
+      : w00(((const double2*)p.string)[0]), w01(((const double2*)p.string)[1]), w10(((const double2*)p.string)[2]), w11(((const double2*)p.string)[3]) {}
+  // the chains of the operators and, where str is wanted, the pure string chain behind them
+  __device__ __forceinline__ int n_chains(const CorrelatorArgs& p) const { return p.n_ops + (p.str != nullptr ? 1 : 0); }
+  template <int D>
+  __device__ __forceinline__ const double2 (&mixed(const double2 (&y)[2][D], double2 (&z)[2][D]) const)[2][D] {
+    mix_rows<D>(w00, w01, w10, w11, y, z);
+    return z;
+  }
+  template <class Apply>
+  __device__ __forceinline__ double2 step(Apply&& apply) const {
+    return apply(w00, w01, w10, w11, false);
+  }
+};
+
 constexpr int kRowTile = 8;   // steps gathered in LDS before they are stored: runs of 128 bytes along n
 
-template <int D>
+template <int D, class Chain>
 __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
   constexpr int EV = 64 / D;       // evaluations per workgroup (one wave)
   __shared__ double2 sL[kMaxObservableOps][D][64];             // L_a[i][q] of the lane that owns row q: [a][i][lane]
@@ -47,6 +105,7 @@ __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
   const double2* Ab = (const double2*)p.A + b * (2 * D * D);
   const double2* O = (const double2*)p.ops;          // [n_ops][2][2], uniform addresses
   const int n_ops = p.n_ops, n_max = p.n_max;
+  const Chain chain(p);
 
   double2 A[2][D][D];
 #pragma unroll
@@ -159,26 +218,30 @@ __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
     }
   }
 
-  for (int c = 0; c < n_ops; ++c) {
+  // The chains of the n_ops right operators, one after the other: x = E_(O_c)(r), then n_max times the n_ops read-outs, each followed
+  // by one step of the chain; the values of (evaluation bb, read-out a) are the row (bb n_out + a) row_len of `rows`.
+  // String launches that return str walk one more chain, the pure string chain: it starts from r with the string itself as its first
+  // operator and has one read-out, the plain trace of x - tr(L x) with the identity in the place of L_0, which no chain needs any more.
+  const int n_chains = chain.n_chains(p);
+  for (int c = 0; c < n_chains; ++c) {
+    const bool pure = Chain::kString && c == n_ops;      // (false at compile time in the plain instantiation)
+    const double2* W = pure ? (const double2*)p.string : O + c * 4;
+    const int n_out = pure ? 1 : n_ops;
+    double2* rows = pure ? (double2*)p.str : (double2*)p.C + (int64_t)c * n_max;
+    const int64_t row_len = pure ? (int64_t)n_max : (int64_t)n_ops * n_max;
+    if (pure) {
+#pragma unroll
+      for (int i = 0; i < D; ++i) sL[0][i][lane] = make_double2(i == q ? 1.0 : 0.0, 0.0);
+    }
     double2 x[D], y[2][D], z[2][D];
-    // x = E_{O_c}(r): z_s = sum_t O_c[t][s] y_t
 #pragma unroll
     for (int j = 0; j < D; ++j) x[j] = sR[j][lane];
     right_mul(x, y);
-    {
-      const double2 w00 = O[c * 4 + 0], w01 = O[c * 4 + 1], w10 = O[c * 4 + 2], w11 = O[c * 4 + 3];
-#pragma unroll
-      for (int l = 0; l < D; ++l) {
-        z[0][l] = cmul(w00, y[0][l]);
-        cfma(w10, y[1][l], z[0][l]);
-        z[1][l] = cmul(w01, y[0][l]);
-        cfma(w11, y[1][l], z[1][l]);
-      }
-    }
+    mix_rows<D>(W[0], W[1], W[2], W[3], y, z);
     left_mul(z, x);
     for (int n = 0; n < n_max; ++n) {
       const int k = n % kRowTile;
-      for (int a = 0; a < n_ops; ++a) {
+      for (int a = 0; a < n_out; ++a) {
         const double2 v = read_out(a, x);
         if (q == 0) sOut[e][a][k] = v;
       }
@@ -186,16 +249,16 @@ __global__ __launch_bounds__(64) void correlator_rows_kernel(CorrelatorArgs p) {
         // the wave stores the tile: kRowTile consecutive lanes write one run of steps of one (evaluation, a)
         __syncthreads();
         const int nb = k + 1, n0 = n - k;
-        for (int idx = lane; idx < EV * n_ops * kRowTile; idx += 64) {
-          const int kk = idx % kRowTile, ea = idx / kRowTile, a = ea % n_ops, ee = ea / n_ops;
+        for (int idx = lane; idx < EV * n_out * kRowTile; idx += 64) {
+          const int kk = idx % kRowTile, ea = idx / kRowTile, a = ea % n_out, ee = ea / n_out;
           const int64_t bb = b0 + ee;
-          if (kk < nb && bb < p.B) ((double2*)p.C)[((bb * n_ops + a) * n_ops + c) * (int64_t)n_max + n0 + kk] = sOut[ee][a][kk];
+          if (kk < nb && bb < p.B) rows[(bb * n_out + a) * row_len + n0 + kk] = sOut[ee][a][kk];
         }
         __syncthreads();
       }
       if (n + 1 < n_max) {
         right_mul(x, y);
-        left_mul(y, x);
+        left_mul(chain.template mixed<D>(y, z), x);
       }
     }
   }
@@ -228,7 +291,7 @@ __device__ __forceinline__ void block_sum_n(double (&v)[2 * kMaxObservableOps], 
   }
 }
 
-template <int D>
+template <int D, class Chain>
 __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p) {
   constexpr int N = D * D, P = D + 1, NW = (N + 63) / 64;
   __shared__ double2 sA[2][D][P];
@@ -241,6 +304,7 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
   if (b >= p.B) return;
   const double2* O = (const double2*)p.ops;
   const int n_ops = p.n_ops, n_max = p.n_max;
+  const Chain chain(p);
   {
     const double2* a = (const double2*)p.A + b * (2 * N);
     sA[0][i][j] = a[tid];
@@ -309,66 +373,81 @@ __global__ __launch_bounds__(D* D) void correlator_block_kernel(CorrelatorArgs p
       for (int k = 0; k < D; ++k) cfma_conj(sZ[t][i][k], sA[t][j][k], out);
     return out;
   };
-  // tr(L_a x) / tr r for every a, in every thread
-  auto read_out = [&](const double2 x) {
+  // tr(L_a x) for the first n_out of the L_a, in v of every thread
+  auto read_out = [&](const double2 x, const int n_out) {
 #pragma unroll
     for (int a = 0; a < kMaxObservableOps; ++a) {
       const double2 w = cmul(Lji[a], x);
       v[2 * a] = w.x;
       v[2 * a + 1] = w.y;
     }
-    block_sum_n<D>(v, 2 * n_ops, sRed, tid);
+    block_sum_n<D>(v, 2 * n_out, sRed, tid);
   };
 
   if (p.one != nullptr) {
-    read_out(r);
+    read_out(r, n_ops);
 #pragma unroll
     for (int a = 0; a < kMaxObservableOps; ++a)
       if (a < n_ops && tid == 0) ((double2*)p.one)[b * n_ops + a] = cmul(make_double2(v[2 * a], v[2 * a + 1]), inv);
   }
 
-  const double2 zero = make_double2(0.0, 0.0);
-  for (int c = 0; c < n_ops; ++c) {
+  // The chains of the n_ops right operators, one after the other: x = E_(O_c)(r), then n_max times the n_ops read-outs, each followed
+  // by one step of the chain; the values of read-out a are the row a row_len of `rows`.  String launches that return str walk one more
+  // chain, the pure string chain: it starts from r with the string itself as its first operator and has one read-out, the plain trace
+  // of x - tr(L x) with the identity in the place of L_0, which no chain needs any more.
+  const int n_chains = chain.n_chains(p);
+  for (int c = 0; c < n_chains; ++c) {
+    const bool pure = Chain::kString && c == n_ops;      // (false at compile time in the plain instantiation)
+    const double2* W = pure ? (const double2*)p.string : O + c * 4;
+    const int n_out = pure ? 1 : n_ops;
+    double2* rows = pure ? (double2*)p.str + b * (int64_t)n_max : (double2*)p.C + (b * n_ops * n_ops + c) * (int64_t)n_max;
+    const int64_t row_len = pure ? (int64_t)n_max : (int64_t)n_ops * n_max;
+    if (pure) Lji[0] = make_double2(i == j ? 1.0 : 0.0, 0.0);
     __syncthreads();
     sX[i][j] = r;
     __syncthreads();
-    double2 x = apply(O[c * 4 + 0], O[c * 4 + 1], O[c * 4 + 2], O[c * 4 + 3], false);
+    double2 x = apply(W[0], W[1], W[2], W[3], false);
     for (int n = 0; n < n_max; ++n) {
       const int k = n % kBlockTile;
-      read_out(x);
+      read_out(x, n_out);
       if (tid == 0) {
 #pragma unroll
         for (int a = 0; a < kMaxObservableOps; ++a)
-          if (a < n_ops) sOut[a][k] = cmul(make_double2(v[2 * a], v[2 * a + 1]), inv);
+          if (a < n_out) sOut[a][k] = cmul(make_double2(v[2 * a], v[2 * a + 1]), inv);
       }
       if (k == kBlockTile - 1 || n == n_max - 1) {
         __syncthreads();
         const int nb = k + 1, n0 = n - k, a = tid / kBlockTile, kk = tid % kBlockTile;
-        if (a < n_ops && kk < nb) ((double2*)p.C)[((b * n_ops + a) * n_ops + c) * (int64_t)n_max + n0 + kk] = sOut[a][kk];
+        if (a < n_out && kk < nb) rows[a * row_len + n0 + kk] = sOut[a][kk];
         __syncthreads();
       }
       if (n + 1 < n_max) {
         sX[i][j] = x;
         __syncthreads();
-        x = apply(zero, zero, zero, zero, true);
+        x = chain.step(apply);
       }
     }
   }
 }
 
-}  // namespace
-
-hipError_t launch_correlators(int D, const CorrelatorArgs& a, hipStream_t st) {
+template <class Chain>
+hipError_t launch_chain(int D, const CorrelatorArgs& a, hipStream_t st) {
   if (a.B <= 0) return hipSuccess;
   if (a.n_ops < 1 || a.n_ops > kMaxObservableOps || a.n_max < 1) return hipErrorInvalidValue;
+  if (Chain::kString != (a.string != nullptr) || (!Chain::kString && a.str != nullptr)) return hipErrorInvalidValue;
   switch (D) {
-    case 2: hipLaunchKernelGGL(correlator_rows_kernel<2>, dim3((unsigned)((a.B + 31) / 32)), dim3(64), 0, st, a); break;
-    case 4: hipLaunchKernelGGL(correlator_rows_kernel<4>, dim3((unsigned)((a.B + 15) / 16)), dim3(64), 0, st, a); break;
-    case 8: hipLaunchKernelGGL(correlator_block_kernel<8>, dim3((unsigned)a.B), dim3(64), 0, st, a); break;
-    case 16: hipLaunchKernelGGL(correlator_block_kernel<16>, dim3((unsigned)a.B), dim3(256), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((correlator_rows_kernel<2, Chain>), dim3((unsigned)((a.B + 31) / 32)), dim3(64), 0, st, a); break;
+    case 4: hipLaunchKernelGGL((correlator_rows_kernel<4, Chain>), dim3((unsigned)((a.B + 15) / 16)), dim3(64), 0, st, a); break;
+    case 8: hipLaunchKernelGGL((correlator_block_kernel<8, Chain>), dim3((unsigned)a.B), dim3(64), 0, st, a); break;
+    case 16: hipLaunchKernelGGL((correlator_block_kernel<16, Chain>), dim3((unsigned)a.B), dim3(256), 0, st, a); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
+
+}  // namespace
+
+hipError_t launch_correlators(int D, const CorrelatorArgs& a, hipStream_t st) { return launch_chain<PlainChain>(D, a, st); }
+hipError_t launch_string_correlators(int D, const CorrelatorArgs& a, hipStream_t st) { return launch_chain<StringChain>(D, a, st); }
 
 }  // namespace qmps

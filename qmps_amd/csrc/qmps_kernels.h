@@ -457,8 +457,12 @@ struct CorrelatorArgs {
   void* one;           // nullable [B][n_ops] complex: <O_a>
   int64_t B;
   int n_ops, n_max;    // 1 <= n_ops <= kMaxObservableOps, n_max >= 1
+  const void* string;  // string launch only (null in the plain one): [2][2] complex, S[t][s] = <t|S|s> (device)
+  void* str;           // string launch only, nullable [B][n_max] complex: <S(1) .. S(n)>, n = 1 .. n_max
 };
 hipError_t launch_correlators(int D, const CorrelatorArgs& a, hipStream_t st);
+// the same kernels with E_S as the step of every chain in the place of T (C: <O_a(0) S(1) .. S(n-1) O_c(n)>) and the pure string chain
+hipError_t launch_string_correlators(int D, const CorrelatorArgs& a, hipStream_t st);
 // Schmidt spectra (qmps_entanglement.hip): batched complex-Hermitian Jacobi, one launch
 struct EntanglementArgs {
   const void* r;       // [B][D][D] complex right environments (herm(r) / tr r is diagonalised)

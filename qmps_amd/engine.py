@@ -280,21 +280,42 @@ class EnergyEngine:
         L.check(self._lib.qmps_get_rdm(self._ctx, B, _f64(rho.view(np.float64))))
         return rho
 
-    def correlators(self, ops, n_max, B=None, want_one_site=False):
+    def correlators(self, ops, n_max, B=None, want_one_site=False, string=None, want_string=False):
         """Two-point functions of the resident states with their resident environments (`launch` with the environments stored, or
         `set_env_guess`; nothing is solved here): C[b, a, c, n - 1] = <O_a(site 0) O_c(site n)> for n = 1 .. n_max, shape
         (B, m, m, n_max) complex128.  ops: (m, 2, 2) array-like or one (2, 2) matrix, O[t, s] = <t|O|s>, 1 <= m <= 4, need not be
-        Hermitian.  want_one_site=True: returns (C, one) with one[b, a] = <O_a>, shape (B, m).  One kernel launch, one synchronisation."""
+        Hermitian.  want_one_site=True: returns (C, one) with one[b, a] = <O_a>, shape (B, m).  One kernel launch, one synchronisation.
+        string: a (2, 2) matrix S placed on every site between the two operators (qmps_string_correlators),
+        C[b, a, c, n - 1] = <O_a(0) S(1) .. S(n-1) O_c(n)>; want_string=True (it needs a string) appends str[b, n - 1] = <S(1) .. S(n)>,
+        shape (B, n_max), to the returned tuple.  Still one launch and one synchronisation."""
         B = self.B if B is None else int(B)
         ops = _one_site_ops(ops)
         m, n_max = ops.shape[0], int(n_max)
-        size = max(B, 0) * m * m * max(n_max, 0)
+        size = max(B, 0) * (m * m + bool(want_string)) * max(n_max, 0)
+        fits = 0 <= size <= (1 << 26)
         # (the library checks the sizes before anything is written: an array it refuses is never touched)
-        C = np.empty((B, m, m, n_max) if 0 <= size <= (1 << 26) else (0,), dtype=np.complex128)
+        C = np.empty((B, m, m, n_max) if fits else (0,), dtype=np.complex128)
         one = np.empty((max(B, 0), m), dtype=np.complex128) if want_one_site else None
-        L.check(self._lib.qmps_correlators(self._ctx, B, m, _f64(ops.view(np.float64)), n_max, _f64(C.view(np.float64)),
-                                           None if one is None else _f64(one.view(np.float64))))
-        return (C, one) if want_one_site else C
+        one_p = None if one is None else _f64(one.view(np.float64))
+        if string is None:
+            if want_string:
+                raise ValueError('correlators: want_string=True needs a string')
+            L.check(self._lib.qmps_correlators(self._ctx, B, m, _f64(ops.view(np.float64)), n_max, _f64(C.view(np.float64)), one_p))
+            return (C, one) if want_one_site else C
+        S = np.ascontiguousarray(np.asarray(string, dtype=np.complex128))
+        if S.shape != (2, 2):
+            raise ValueError(f'string: expected shape (2, 2), got {S.shape}')
+        st = np.empty((B, n_max) if fits else (0,), dtype=np.complex128) if want_string else None
+        L.check(self._lib.qmps_string_correlators(self._ctx, B, m, _f64(ops.view(np.float64)), _f64(S.view(np.float64)), n_max,
+                                                  _f64(C.view(np.float64)), one_p, None if st is None else _f64(st.view(np.float64))))
+        out = (C,) + ((one,) if want_one_site else ()) + ((st,) if want_string else ())
+        return out if len(out) > 1 else C
+
+    def string_order(self, string, n_max, B=None):
+        """String order of the resident states: str[b, n - 1] = <S(1) .. S(n)> for n = 1 .. n_max, shape (B, n_max) complex128, for the
+        one-site operator S = string, a (2, 2) matrix (X: the disorder parameter of the transverse-field Ising chain).  One call of
+        `correlators` with the string as its single operator."""
+        return self.correlators(string, n_max, B=B, string=string, want_string=True)[1]
 
     def correlator_sums(self, ops, z, B=None, want_one_site=False, want_site=False):
         """Sums over all distances of the connected two-point functions of the resident states (`launch` with the environments stored,

@@ -446,6 +446,21 @@ def correlation_functions(params, ops, n_max, D=2, state_tensor=ShallowCNOTState
     return C, one, status
 
 
+def string_correlators(params, ops, string, n_max, D=2, state_tensor=ShallowCNOTStateTensor):
+    """String order of the states of K parameter rows - the companion of `correlation_functions` (params = out['params'] of
+    `ground_state_sweep`), with the one-site operator `string` = S, a (2, 2) matrix, on every site between the two operators:
+      C (K, m, m, n_max)   C[k, a, c, n - 1] = <O_a(site 0) S(1) .. S(n-1) O_c(site n)>, n = 1 .. n_max
+      one (K, m)           <O_a>
+      str (K, n_max)       str[k, n - 1] = <S(1) .. S(n)>: with S = X the disorder parameter of the transverse-field Ising chain
+      status (K,)          of the environment solve (STATUS_OK = 0; the values of any other row are not to be trusted)
+    ops as in `correlation_functions`.  Jordan-Wigner fermion functions are combinations of C with S = X (examples/string_order.py).
+    One environment solve with the environments stored, then ONE launch of the correlator kernel with E_S as the step of every chain
+    (`EnergyEngine.correlators` with `string`)."""
+    eng, K = _resident_states(params, D, state_tensor)
+    C, one, st = eng.correlators(ops, n_max, B=K, want_one_site=True, string=string, want_string=True)
+    return C, one, st, eng.results_status(K)
+
+
 def entanglement_entropy(params, D=2, state_tensor=ShallowCNOTStateTensor):
     """Half-chain entanglement of the states of K parameter rows - the companion of `ground_state_sweep` (params = out['params']) and
     `correlation_functions`:
