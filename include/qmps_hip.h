@@ -149,7 +149,8 @@ extern "C" {
  *   QMPS_NO_FUSED_ANSATZ  D = 4: materialise ansatz-built tensors in HBM instead of building them inside the energy kernel
  *   QMPS_NO_GRAPH         rotosolve / time evolution: plain launches instead of a captured hipGraph per sweep
  *   QMPS_OVERLAP_POWER    D = 4 overlap objective: operator-form power method instead of squaring the 16 x 16 map
- *   QMPS_D16_BLOCK        D = 16: the generic LDS-tile kernels instead of the matrix-core kernels
+ *   QMPS_D16_BLOCK        D = 16: the generic LDS-tile kernels instead of the matrix-core kernels (the environment solve of the energy
+ *                         path hands over to the Krylov fall-back as the matrix-core kernel does; it ran the power iteration alone)
  *   QMPS_NO_DEFLATION     D = 8, 16 overlap objective: plain power method, without the occasional shifted step that removes a slowly
  *                         decaying second eigenvector (same results; candidates with |eta_2 / eta_1| > 0.9 take 2 - 10 x more steps;
  *                         D = 16: cold starts only - warm-started batches run the lean loop)

@@ -143,8 +143,11 @@ int energy_power(qmps_ctx* c, qmps::LaneArgs& a, int flags, KernelTimer& t) {
   // PowerCircuit); QMPS_NO_KRYLOV switches it off.  On request only (QMPS_FLAG_KRYLOV_FALLBACK; the one-shot entry points set it): the
   // two extra launches - nearly always empty - cost 3.1 - 3.4 us of a 16 - 20 us step of resident tensors (B = 96 / 768, measured),
   // nothing next to the round trips of a one-shot call.
-  const bool krylov = c->D == 8 && (flags & QMPS_FLAG_KRYLOV_FALLBACK) != 0 && solver != QMPS_ENV_POWER &&
-                      documented_switch("QMPS_NO_KRYLOV") == nullptr && a.max_iter > 64 && c->d_queue != nullptr && a.r_out != nullptr;
+  // D = 16 under QMPS_D16_BLOCK: the same computation as energy_mfma_d16, so the hand-over is armed as it is there - whatever the solver
+  // and without the flag (include/qmps_hip.h: "D = 16 always hands over").  It used to run the power iteration alone: status 1 at max_iter
+  // where the matrix-core path returns status 0 (tests/test_gap_gpu.py).
+  const bool wanted = c->D == 16 || (c->D == 8 && (flags & QMPS_FLAG_KRYLOV_FALLBACK) != 0 && solver != QMPS_ENV_POWER);
+  const bool krylov = wanted && documented_switch("QMPS_NO_KRYLOV") == nullptr && a.max_iter > 64 && c->d_queue != nullptr && a.r_out != nullptr;
   HIP_TRY(t.start());
   if (int rc = power_with_krylov(c, a, krylov, qmps::launch_energy)) return rc;
   HIP_TRY(t.stop());

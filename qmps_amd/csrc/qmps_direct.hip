@@ -29,6 +29,7 @@
 #include "qmps_circuit.h"
 #include "qmps_direct_core.h"
 #include "qmps_direct_d8.h"
+#include "qmps_power_d4_core.h"
 
 namespace qmps {
 
@@ -551,8 +552,8 @@ __global__ __launch_bounds__(64, LEAN ? QMPS_ENERGY_ONLY_LEAN_WAVES : 2) void en
 //     (964 steps x 1.7 us of a lane's 1 000-instruction step: 1.65 ms per 65 536 evaluations, 0.12 of the FP64 roofline).  Here a row
 //     whose evaluation has converged stores its environment and draws the next one (wave-aggregated: one atomic per refill round), and a
 //     straggler costs its step latency (~0.1 us), not a lane's.
-// Same iterate sequence as the lane kernel up to rounding (r_0 = 1/D or the caller's guess, symmetrised and trace-normalised; stop when
-// ||r_k - r_(k-1)||_F < tol; iterations = k; status 1 at max_iter).  The energies, the positive-definiteness test and the cost sums
+// Same iterate sequence as the lane kernel, bit for bit: both take their arithmetic from qmps_power_d4_core.h (r_0 = 1/D or the caller's
+// guess, symmetrised and trace-normalised; stop when ||r_k - r_(k-1)||_F < tol; iterations = k; status 1 at max_iter).  The energies, the positive-definiteness test and the cost sums
 // follow in energy_only_d4_kernel (check_pd) on the stored environments.
 // ------------------------------------------------------------------------------------------
 #ifndef QMPS_POWER_D4_MINWAVES
@@ -571,7 +572,7 @@ __global__ __launch_bounds__(64, QMPS_POWER_D4_MINWAVES) void env_power_d4_kerne
   constexpr int PAD = 512 + 16, SLOTS = 4, kChunk = 8;
   __shared__ __attribute__((aligned(16))) unsigned char lds[SLOTS * PAD];
   const int lane = threadIdx.x, g = lane >> 4, c = lane & 15, i = c >> 2, ip = c & 3;
-  const bool diag = i == ip, rot = i > ip;
+  const bool diag = i == ip;
   const double wt = diag ? 1.0 : 2.0;                                  // ||r||_F^2 = sum_diag u^2 + 2 sum_offdiag u^2
   const double tol2 = p.tol * p.tol;
   const unsigned long long below = (1ull << (lane & ~15)) - 1ull;      // the lanes of the rows in front of this one
@@ -619,54 +620,12 @@ __global__ __launch_bounds__(64, QMPS_POWER_D4_MINWAVES) void env_power_d4_kerne
             w[c + 16] = v1;
           }
           __builtin_amdgcn_wave_barrier();          // (the tile is private to the row; LDS is in order per wave)
-          // row c = (i, i') of the real transfer matrix (DirectD4::build for one row): with P(j,j') = sum_s (gamma A_s[i][j]) conj(A_s[i'][j']),
-          // gamma = 1 (i <= i') | i (i > i'):  column (j,j): Re P(j,j);  (lo,hi): Re (P(lo,hi) + P(hi,lo));  (hi,lo): -Im (P(lo,hi) - P(hi,lo))
-          double tr[2][4], ti[2][4], br[2][4], bi[2][4];
-#pragma unroll
-          for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const double2 a = tile[(4 * s + i) * 4 + j], cc = tile[(4 * s + ip) * 4 + j];
-              tr[s][j] = rot ? -a.y : a.x;
-              ti[s][j] = rot ? a.x : a.y;
-              br[s][j] = cc.x;
-              bi[s][j] = cc.y;
-            }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            double v = tr[0][j] * br[0][j];
-            v = dfma(ti[0][j], bi[0][j], v);
-            v = dfma(tr[1][j], br[1][j], v);
-            v = dfma(ti[1][j], bi[1][j], v);
-            R[5 * j] = v;
-          }
-#pragma unroll
-          for (int lo = 0; lo < 4; ++lo)
-#pragma unroll
-            for (int hi = lo + 1; hi < 4; ++hi) {
-              double re = tr[0][lo] * br[0][hi], im = tr[0][lo] * bi[0][hi];
-#pragma unroll
-              for (int s = 0; s < 2; ++s) {
-                if (s > 0) {
-                  re = dfma(tr[s][lo], br[s][hi], re);
-                  im = dfma(tr[s][lo], bi[s][hi], im);
-                }
-                re = dfma(ti[s][lo], bi[s][hi], re);
-                re = dfma(tr[s][hi], br[s][lo], re);
-                re = dfma(ti[s][hi], bi[s][lo], re);
-                im = dfma(-ti[s][lo], br[s][hi], im);
-                im = dfma(ti[s][hi], br[s][lo], im);
-                im = dfma(-tr[s][hi], bi[s][lo], im);
-              }
-              R[4 * lo + hi] = re;
-              R[4 * hi + lo] = im;
-            }
+          // row c = (i, i') of the real transfer matrix (qmps_power_d4_core.h: the same operations as the lane kernel's)
+          power_d4_map_row([tile](int s, int a, int j) { return tile[(4 * s + a) * 4 + j]; }, i, ip, R);
           // start vector: 1/D, or the caller's guess (qmps_set_env_guess) symmetrised and trace-normalised - zeros / NaN / nothing stored: 1/D
           u = diag ? 0.25 : 0.0;
           if constexpr (GUESS) {
-            const double2* rin = (const double2*)p.r_in + b * 16;
-            const double2 rw = rin[4 * i + ip], cl = rin[4 * ip + i];       // r[i][i'], r[i'][i]
-            const double ug = i <= ip ? 0.5 * (rw.x + cl.x) : 0.5 * (cl.y - rw.y);   // Re r[i][i'] (i <= i') | Im r[i'][i] (i > i')
+            const double ug = power_d4_guess_coord((const double2*)p.r_in + b * 16, i, ip);
             const double t = row16_sum(diag ? ug : 0.0);
             const bool usable = t > 1e-300 && t < 1e300;
             if (usable) u = ug * (1.0 / t);
@@ -690,7 +649,7 @@ __global__ __launch_bounds__(64, QMPS_POWER_D4_MINWAVES) void env_power_d4_kerne
     row_fmac<8>(y0, u, R[8]);       row_fmac<9>(y1, u, R[9]);   row_fmac<10>(y2, u, R[10]); row_fmac<11>(y3, u, R[11]);
     row_fmac<12>(y0, u, R[12]);     row_fmac<13>(y1, u, R[13]); row_fmac<14>(y2, u, R[14]); row_fmac<15>(y3, u, R[15]);
     const double d = u - up;
-    const double d2 = row16_sum(wt * d * d);       // ||r_k - r_(k-1)||_F^2
+    const double d2 = row16_sum(power_d4_distance_share(wt, d));       // ||r_k - r_(k-1)||_F^2, the same bits in every lane of the row
     const double y = (y0 + y1) + (y2 + y3);
     double t0 = 0.0, t1 = 0.0;                     // the trace: the diagonal coordinates sit in lanes 0, 5, 10, 15 of the row
     row_fmac<0, true>(t0, y, 1.0); row_fmac<5>(t1, y, 1.0); row_fmac<10>(t0, y, 1.0); row_fmac<15>(t1, y, 1.0);

@@ -13,13 +13,16 @@
 #include "qmps_kernels.h"
 #include "qmps_device.h"
 #include "qmps_lane_core.h"
+#include "qmps_power_d4_core.h"
 #include "qmps_circuit.h"       // Reg, ansatz_circuit_cs, ansatz_param_scale, roto_shift_value
 #include "qmps_roto_math.h"     // wrap_pi, double_sinusoid_step
 
 namespace qmps {
 
-template <int D, bool SOLVE>
+// ROWMATH (D = 4, SOLVE, no squaring tail behind it): the plain power iteration with the arithmetic of env_power_d4_kernel
+template <int D, bool SOLVE, bool ROWMATH = false>
 __global__ __launch_bounds__(64) void energy_lane_kernel(LaneArgs p) {
+  static_assert(!ROWMATH || (D == 4 && SOLVE), "ROWMATH: the D = 4 solve only");
   using Cfg = LaneCfg<D>;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int lane = threadIdx.x;
@@ -119,7 +122,40 @@ __global__ __launch_bounds__(64) void energy_lane_kernel(LaneArgs p) {
     bool active = valid;
     const double tol2 = p.tol * p.tol;
     const bool hybrid = p.hybrid != 0 && p.handoff < p.max_iter;
-    const int plain = hybrid ? p.handoff : p.max_iter;
+    int plain = hybrid ? p.handoff : p.max_iter;
+    if constexpr (ROWMATH) {
+      // QMPS_ENV_POWER at D = 4 (QMPS_POWER_LANE, or a context without the work counter of env_power_d4_kernel): the iteration in the
+      // real coordinates and with the operations of that kernel (qmps_power_d4_core.h) - the same iterates, iteration counts and
+      // statuses bit for bit, which two differently rounded iterations cannot give where the residual creeps towards tol
+      double u[16];
+#pragma unroll
+      for (int c = 0; c < 16; ++c) u[c] = (c >> 2) == (c & 3) ? 0.25 : 0.0;
+      if (p.r_in != nullptr && valid) {
+        const double2* rin = (const double2*)p.r_in + b * 16;
+        double ug[16];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) ug[c] = power_d4_guess_coord(rin, c >> 2, c & 3);
+        const double t = (ug[0] + ug[10]) + (ug[5] + ug[15]);       // row16_sum of the diagonal coordinates
+        const bool usable = t > 1e-300 && t < 1e300;
+        const double inv = 1.0 / t;
+#pragma unroll
+        for (int c = 0; c < 16; ++c)
+          if (usable) u[c] = ug[c] * inv;
+      }
+      bool converged = false;
+      if (active)
+        power_d4_lane_solve([&](int s, int a, int j) { return make_double2(are[s][a][j], aim[s][a][j]); }, u, p.max_iter, tol2, iters, converged);
+      if (converged) status = QMPS_ST_OK;
+      active = false;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = i; j < 4; ++j) {
+          rre[i][j] = u[4 * i + j];
+          rim[i][j] = i == j ? 0.0 : u[4 * j + i];
+        }
+      plain = 0;
+    }
     // two steps per trip, ping-pong r -> n -> r: frozen (converged) lanes are simply masked off
     for (int k = 1; k <= plain; k += 2) {
       if (!__any(active)) break;
@@ -240,7 +276,10 @@ template <int D>
 static hipError_t launch_lane(const LaneArgs& a, bool solve, hipStream_t st) {
   const int grid = (int)((a.B + 63) / 64);
   const size_t lds = LaneCfg<D>::kLdsBytes;
-  if (solve)
+  const bool tail = a.hybrid != 0 && a.handoff < a.max_iter;       // (the kernel's own `hybrid`)
+  if (solve && D == 4 && !tail)
+    hipLaunchKernelGGL((energy_lane_kernel<D, true, D == 4>), dim3(grid), dim3(64), lds, st, a);
+  else if (solve)
     hipLaunchKernelGGL((energy_lane_kernel<D, true>), dim3(grid), dim3(64), lds, st, a);
   else
     hipLaunchKernelGGL((energy_lane_kernel<D, false>), dim3(grid), dim3(64), lds, st, a);

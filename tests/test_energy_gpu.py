@@ -448,7 +448,8 @@ def test_plain_power_iteration_d4_row_kernel_against_the_lane_kernel_and_the_ora
     """Round 6: QMPS_ENV_POWER at D = 4 runs env_power_d4_kernel - a 16-lane DPP row per evaluation (the map as a real 16 x 16 matrix in
     registers, a power step = sixteen v_fmac_f64_dpp), persistent waves drawing evaluations from a work counter - then the energy-only
     kernel.  Against the lane-per-evaluation kernel of rounds 1-5 (QMPS_POWER_LANE=1) and the C oracle (plain power iteration): the same
-    iterates (1e-12), the same iteration counts (+-1: a borderline test), statuses, energies (1e-10), density matrices, summed costs; batch
+    iterates (1e-12), the same iteration counts (the lane kernel's exactly - the two share their arithmetic, qmps_power_d4_core.h -, the oracle's +-1: a
+    borderline test), statuses, energies (1e-10), density matrices, summed costs; batch
     sizes that are no multiple of four, a batch of one, an iteration cap that some evaluations hit (status 1 with the iterate of the last
     step), the caller's guess (symmetrised, trace-normalised; an unusable one = the default start), a resident-batch window, the in-kernel
     cost accumulator, a tensor that is not an isometry and the zero tensor (no fixed point: status 1, not a hang)."""
@@ -472,7 +473,7 @@ def test_plain_power_iteration_d4_row_kernel_against_the_lane_kernel_and_the_ora
         new, old = run(A, False, max_iter=4000), run(A, True, max_iter=4000)
         ref = c_oracle.energy_batch(A, h, max_iter=4000, want_r=True, want_rho=True)
         assert np.array_equal(new[2], old[2]) and np.all(new[2] == ref['status'])
-        assert np.abs(new[1] - old[1]).max() <= 1 and np.abs(new[1] - ref['iters']).max() <= 1 and (new[1] == ref['iters']).mean() > 0.95
+        assert np.array_equal(new[1], old[1]) and np.abs(new[1] - ref['iters']).max() <= 1 and (new[1] == ref['iters']).mean() > 0.95
         ok = new[2] == 0
         assert np.abs(new[0] - old[0])[ok].max() < 1e-12 and np.abs(new[0] - ref['E'])[ok].max() < E_TOL
         assert np.abs(new[3] - old[3])[ok].max() < 1e-12 and np.abs(new[3] - ref['r'])[ok].max() < R_TOL
@@ -489,7 +490,7 @@ def test_plain_power_iteration_d4_row_kernel_against_the_lane_kernel_and_the_ora
     guess[::7] = 0.0
     guess[3::7] = np.nan
     gn, go = run(A, False, r0=guess), run(A, True, r0=guess)
-    assert np.all(gn[2] == 0) and np.abs(gn[1] - go[1]).max() <= 1 and np.abs(gn[3] - full[3]).max() < 1e-10 and np.abs(gn[0] - full[0]).max() < E_TOL
+    assert np.all(gn[2] == 0) and np.array_equal(gn[1], go[1]) and np.abs(gn[3] - full[3]).max() < 1e-10 and np.abs(gn[0] - full[0]).max() < E_TOL
     usable = np.ones(len(A), dtype=bool)
     usable[::7] = False
     usable[3::7] = False
