@@ -167,6 +167,11 @@ extern "C" {
  *   QMPS_POWER_LANE       D = 4, QMPS_ENV_POWER: one LANE per evaluation (rounds 1-5: a wave waits for the slowest of its 64 evaluations)
  *                         instead of a DPP quad per evaluation in persistent waves that draw their evaluations from a work counter
  *                         (round 6; same iterates, same iteration counts and statuses; energies to rounding)
+ *   QMPS_WAVE_SLOTS       D = 4, QMPS_ENV_DIRECT: the fused kernel paces the two waves of a SIMD by static priority - in a grid of more than
+ *                         one generation of resident waves the last half generation starts at s_setprio 1 and hands the priority back behind
+ *                         its solve (same arithmetic, same results bit for bit).  0 switches pacing off; a positive value stands for the
+ *                         number of resident wave slots, which otherwise comes from the occupancy of the kernel times the CU count (the
+ *                         tests set 4, so that a handful of workgroups crosses every branch).  Read on every launch.
  * Everything else that used to be tunable from the environment (thresholds, schedules: profiles/EXPERIMENTS.md) is compiled
  * in only with -DQMPS_DEBUG_KNOBS; the shipped library ignores those variables (tests/test_cabi.py checks both lists). */
 
@@ -201,8 +206,7 @@ int qmps_abi_version(void);
  *      connected two-point functions (structure factors).
  *      qmps_correlator_sums_two_site, the same sums for two-site operators (energy-density structure factors, the energy variance per site).
  *      qmps_string_correlators, the two-point functions with a one-site string between their ends and the string order itself (disorder
- *      parameters, Jordan-Wigner fermion functions).
- *      Changed later without a bump (same signatures; nothing a caller can detect beforehand, a refusal is an error code):
+ *      parameters, Jordan-Wigner fermion functions). *      Changed later without a bump (same signatures; nothing a caller can detect beforehand, a refusal is an error code):
  *      RESIDENT RESULTS (below): the context knows per evaluation slot, not per context, what its buffers hold, and read-backs that used to return
  *      whatever the buffer held now fail with QMPS_ERR_STATE (same signatures).  qmps_get_env, qmps_get_rdm, qmps_energy_only_launch, qmps_correlators,
  *      qmps_entanglement, qmps_correlator_sums: on a window no launch has stored environments for (another window had them), and after a

@@ -77,6 +77,9 @@ int energy_direct_d4(qmps_ctx* c, qmps::LaneArgs& a, int flags, KernelTimer& t) 
   a.r_out = (flags & QMPS_FLAG_NO_ENV_OUT) ? nullptr : win_r(c);
   if (int rc = cost_sink(c, a, flags & QMPS_FLAG_ACCUMULATE_COST, (a.B + 15) / 16, 16)) return rc;
   c->dominant = "energy_direct_d4_kernel";
+#ifdef QMPS_WAVE_TIMELINE
+  a.timeline = c->d_timeline;
+#endif
   HIP_TRY(t.start());
   HIP_TRY(qmps::launch_energy_direct_d4(a, c->stream));
   HIP_TRY(t.stop());

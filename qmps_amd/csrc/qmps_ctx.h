@@ -188,6 +188,7 @@ struct qmps_ctx {
   qmps_slots overlap_x;             // d_r holds the fixed points of THAT launch (have_overlap_x: of some launch - enough for a warm start)
   bool have_overlap_x = false;       // d_r holds the fixed points of the last overlap launch (QMPS_OVERLAP_WANT_R)
   bool want_rho = false;
+  unsigned long long* d_timeline = nullptr;   // qmps_wave_timeline, during its call only: where the fused D = 4 kernel stamps its waves
   bool defer_sync = false;          // one-shot entry points: the setters leave their H2D copies in flight, ONE synchronisation at the end
   // rotosolve work buffers and the captured sweep are kept between calls (a call used to spend ~0.6 ms on hipMalloc /
   // hipFree / graph capture + instantiation - as much as three sweeps at D = 4)

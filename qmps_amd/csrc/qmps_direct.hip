@@ -23,8 +23,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "qmps_hip.h"
 #include "qmps_kernels.h"
+#include "qmps_knobs.h"
 #include "qmps_device.h"
 #include "qmps_circuit.h"
 #include "qmps_direct_core.h"
@@ -195,6 +198,55 @@ __device__ __forceinline__ void squaring_fallback(const unsigned char* tiles, in
   }
 }
 
+// HBM -> LDS: the 16 tensors of a wave are one contiguous 8 KB slab; 16 B per lane per load, eight loads, each 1 KB chunk into the padded
+// tile (item stride 528 B).  A whole slab - every workgroup but the last one of a batch that is no multiple of 16; the test is
+// wave-uniform - issues its eight loads back to back from one address and writes every chunk to LDS as it arrives (the loads return in
+// order: counted vmcnt waits).  These loads are non-temporal: a tensor is read once per launch, and the batches an optimiser cycles
+// through do not fit the caches (measured alone: profiles/wave_pacing_ab.json).  A partial slab loads chunk by chunk under the lane's
+// own bound; evaluations beyond the batch get zeros.
+__device__ __forceinline__ void load_tile16(const unsigned char* slab, int64_t slab_bytes, unsigned char* lds, int lane) {
+  constexpr int ROW = 512, PAD = ROW + 16, CHUNKS = 16 * ROW / 1024;
+  typedef double f64x2 __attribute__((ext_vector_type(2)));
+  double2 v[CHUNKS];
+  // (the writes stand inside both branches: behind their join every one of them would wait for all eight loads)
+  auto to_lds = [&]() {
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) {
+      const int off = c * 1024 + lane * 16;
+      *(double2*)(lds + (off / ROW) * PAD + (off % ROW)) = v[c];
+    }
+  };
+  if (__builtin_amdgcn_readfirstlane((int)slab_bytes) == CHUNKS * 1024) {
+    const unsigned char* src = slab + lane * 16;
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) {
+      const f64x2 w = __builtin_nontemporal_load((const f64x2*)(src + c * 1024));
+      v[c] = make_double2(w.x, w.y);
+    }
+    to_lds();
+    return;
+  }
+#pragma unroll
+  for (int c = 0; c < CHUNKS; ++c) {
+    const int off = c * 1024 + lane * 16;
+    v[c] = make_double2(0.0, 0.0);
+    if (off < slab_bytes) v[c] = *(const double2*)(slab + off);
+  }
+  to_lds();
+}
+
+#ifdef QMPS_WAVE_TIMELINE
+// one word of the wave's timeline record, by lane 0 (LaneArgs::timeline; plain stores)
+#define QMPS_TL_WORD(k, value)                                                                          \
+  do {                                                                                                  \
+    if (p.timeline != nullptr && threadIdx.x == 0) p.timeline[(size_t)blockIdx.x * kTimelineWords + (k)] = (unsigned long long)(value); \
+  } while (0)
+#define QMPS_TL_STAMP(k) QMPS_TL_WORD(k, wall_clock64())
+#else
+#define QMPS_TL_WORD(k, value) ((void)0)
+#define QMPS_TL_STAMP(k) ((void)0)
+#endif
+
 }  // namespace
 
 #ifndef QMPS_DIRECT_MINWAVES
@@ -211,6 +263,17 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
   // reads one address (rows of the partner index) and when its lanes read their own rows (64 B apart)
   __shared__ __attribute__((aligned(16))) unsigned char lds[ITEMS * PAD];
   __shared__ double sq_img[kSqDoubles];      // the rare path's 16 x 16 image
+  // Pacing (LaneArgs::prio_first): VALU issue between the two waves of a SIMD goes by priority, then age, so the last wave of a SIMD
+  // runs alone behind its older partner.  The workgroups from prio_first on start raised and hand the priority back behind the fence
+  // prio_until.  s_setprio is scalar and ignores EXEC: both stand under wave-uniform tests (s_cbranch_scc in the text).
+  {
+    const int blk = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    const bool raise = p.prio_until != kPrioOff && blk >= p.prio_first;
+    if (raise) __builtin_amdgcn_s_setprio(1);
+    QMPS_TL_WORD(kTlRaised, raise ? 1 : 0);
+  }
+  QMPS_TL_STAMP(kTlEntry);
+  QMPS_TL_WORD(kTlCycleEntry, __builtin_readcyclecounter());
   const int lane = threadIdx.x, e = lane >> 2, q = lane & 3;
   const int64_t first = (int64_t)blockIdx.x * ITEMS;
   const int64_t b = first + e;
@@ -260,23 +323,12 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
 #pragma unroll
     for (int xx = 0; xx < 8; ++xx) tile[((xx & 1) * 4 + (xx >> 1)) * 4 + q] = make_double2(reg.re[xx], reg.im[xx]);
   } else {
-    // HBM -> LDS: the wave's 16 tensors are one contiguous 8 KB slab, 16 B per lane per load
     const unsigned char* slab = (const unsigned char*)p.A + first * ROW;
     const int64_t slab_bytes = (p.B - first < ITEMS ? p.B - first : ITEMS) * (int64_t)ROW;
-    double2 v[ITEMS * ROW / 1024];
-#pragma unroll
-    for (int c = 0; c < ITEMS * ROW / 1024; ++c) {
-      const int off = c * 1024 + lane * 16;
-      v[c] = make_double2(0.0, 0.0);
-      if (off < slab_bytes) v[c] = *(const double2*)(slab + off);
-    }
-#pragma unroll
-    for (int c = 0; c < ITEMS * ROW / 1024; ++c) {
-      const int off = c * 1024 + lane * 16;
-      *(double2*)(lds + (off / ROW) * PAD + (off % ROW)) = v[c];
-    }
+    load_tile16(slab, slab_bytes, lds, lane);
   }
   __syncthreads();
+  QMPS_TL_STAMP(kTlTile);
   const QuadOps o{q, (const double2*)(lds + e * PAD)};
   const double tol2 = p.tol * p.tol;
 
@@ -311,12 +363,15 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
     double Rc[4][16], xs[4], y[4];
     Core::build(o, Rc);
     __builtin_amdgcn_sched_barrier(0);     // phase by phase: keeps the operand reads of later phases out of the register file
+    QMPS_TL_STAMP(kTlBuild);
     double pivmax;
     [[maybe_unused]] Core::Set8 own;      // cold start: the acceptance step's first operands, requested in front of the normalisation
     {
       double ur[16];
       Core::solve_gathered(o, Rc, ur, pivmax);
       __builtin_amdgcn_sched_barrier(0);
+      if (p.prio_until == kPrioSolve) __builtin_amdgcn_s_setprio(0);
+      QMPS_TL_STAMP(kTlSolve);
       if constexpr (!WARM) Core::request_own_rows(o, own);
       Core::normalise_gathered(o, ur, us, xs);
     }
@@ -371,6 +426,9 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
   int acc_shards = p.acc_shards;
   asm volatile("" : "+s"(acc_shards));
   __builtin_amdgcn_sched_barrier(0);
+  // (the hand-back of a warm wave whose evaluations all skipped the solve and its fence; nothing new for the others)
+  if (p.prio_until != kPrioOff) __builtin_amdgcn_s_setprio(0);
+  QMPS_TL_STAMP(kTlAccept);
 
   // ---- positive definiteness, two-site density matrix, energies ----
   double pre[4][4], pim[4][4];
@@ -378,6 +436,7 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
   bool pd;
   if constexpr (WARM) pd = Core::density(o, us, p.rho_need, pre, pim);
   else pd = Core::density_sites(o, us, p.rho_need, W, pre, pim);
+  QMPS_TL_STAMP(kTlDensity);
   if (status == QMPS_ST_OK && !pd) status = QMPS_ST_NOT_PD;
   if (p.acc_zero != nullptr && blockIdx.x == 0) acc_clear(p.acc_zero, p.n_terms, lane, 64);   // accumulator of a later step
   for (int t = 0; t < p.n_terms; ++t) {
@@ -431,6 +490,19 @@ __global__ __launch_bounds__(64, QMPS_DIRECT_MINWAVES) void energy_direct_d4_ker
       o2[l] = make_double2(re, im);
     }
   }
+  // (lane 0 belongs to the first evaluation of the tile, which is inside the batch in every workgroup of the grid)
+  QMPS_TL_STAMP(kTlEnd);
+  QMPS_TL_WORD(kTlCycleEnd, __builtin_readcyclecounter());
+  QMPS_TL_WORD(kTlBlock, blockIdx.x);
+#ifdef QMPS_WAVE_TIMELINE
+  if (p.timeline != nullptr && threadIdx.x == 0) {
+    unsigned hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    p.timeline[(size_t)blockIdx.x * kTimelineWords + kTlHwId] = hw;
+    p.timeline[(size_t)blockIdx.x * kTimelineWords + kTlXccId] = xcc;
+  }
+#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -462,14 +534,7 @@ __global__ __launch_bounds__(64, LEAN ? QMPS_ENERGY_ONLY_LEAN_WAVES : 2) void en
   {
     const unsigned char* slab = (const unsigned char*)p.A + first * ROW;
     const int64_t slab_bytes = (p.B - first < ITEMS ? p.B - first : ITEMS) * (int64_t)ROW;
-    double2 v[ITEMS * ROW / 1024];
-#pragma unroll
-    for (int c = 0; c < ITEMS * ROW / 1024; ++c) {
-      const int off = c * 1024 + lane * 16;
-      v[c] = make_double2(0.0, 0.0);
-      if (off < slab_bytes) v[c] = *(const double2*)(slab + off);
-    }
-    // the environment: lane q takes Re r[q][l] (q <= l) | Im r[l][q] (q > l), l = 0 .. 3
+    // the environment: lane q takes Re r[q][l] (q <= l) | Im r[l][q] (q > l), l = 0 .. 3 (requested in front of the tile: loads return in order)
     double x[4];
     {
       const double2* rin = (const double2*)p.r_in + (valid ? b : 0) * 16;
@@ -479,11 +544,7 @@ __global__ __launch_bounds__(64, LEAN ? QMPS_ENERGY_ONLY_LEAN_WAVES : 2) void en
         x[l] = q <= l ? rw.x : cl.y;
       }
     }
-#pragma unroll
-    for (int c = 0; c < ITEMS * ROW / 1024; ++c) {
-      const int off = c * 1024 + lane * 16;
-      *(double2*)(lds + (off / ROW) * PAD + (off % ROW)) = v[c];
-    }
+    load_tile16(slab, slab_bytes, lds, lane);
     __syncthreads();
     const QuadOps o{q, (const double2*)(lds + e * PAD)};
     Core::normalise(o, x);
@@ -780,29 +841,75 @@ hipError_t launch_env_direct_d8(const void* A, void* r_out, int64_t B, hipStream
   return hipGetLastError();
 }
 
+namespace {
+
+// Resident wave slots of the device for one instantiation of the fused kernel - its workgroups are single waves, so workgroups per CU
+// times CUs.  Asked once per device and instantiation.
+template <int ANS, bool WARM>
+hipError_t direct_d4_wave_slots(int64_t* slots) {
+  constexpr int kDevices = 64;
+  static std::atomic<int64_t> known[kDevices];
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev)) return e;
+  const bool cached = dev >= 0 && dev < kDevices;
+  if (cached && known[dev].load(std::memory_order_relaxed) > 0) {
+    *slots = known[dev].load(std::memory_order_relaxed);
+    return hipSuccess;
+  }
+  int per_cu = 0, cus = 0;
+  if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, energy_direct_d4_kernel<ANS, WARM>, 64, 0)) return e;
+  if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) return e;
+  *slots = (int64_t)per_cu * cus;
+  if (cached) known[dev].store(*slots, std::memory_order_relaxed);
+  return hipSuccess;
+}
+
+// The pacing policy (LaneArgs::prio_first), in terms of a workgroup's place in its generation of `slots` resident waves: a grid of more
+// than one generation raises its LAST HALF GENERATION - the workgroups that are dispatched as the younger partner of a SIMD's last pair
+// and would see their partner leave first - from their start to the fence behind their solve: priority outranks age, so a wave raised
+// for its whole life only swaps who runs alone; handed back there, the two waves of the last pair end together.  Timed against the
+// hand-back behind the acceptance step and against the younger half of every generation raised throughout, which gained nothing
+// (profiles/wave_pacing_ab.json).  A grid that fits in one generation has every wave resident from the start and raises nobody.
+// QMPS_WAVE_SLOTS (include/qmps_hip.h): 0 switches pacing off, a positive number stands for the slot count.
+template <int ANS, bool WARM>
+hipError_t pace(LaneArgs& a, int64_t grid) {
+  a.prio_first = 0;
+  a.prio_until = kPrioOff;
+  int64_t slots = 0;
+  if (const char* s = documented_switch("QMPS_WAVE_SLOTS")) {
+    slots = atoll(s);
+  } else if (hipError_t e = direct_d4_wave_slots<ANS, WARM>(&slots)) {
+    return e;
+  }
+  if (slots < 2 || grid <= slots) return hipSuccess;
+  a.prio_first = (int)(grid - slots / 2);
+  a.prio_until = kPrioSolve;
+  return hipSuccess;
+}
+
+template <int ANS, bool WARM>
+hipError_t launch_direct_d4(LaneArgs a, dim3 grid, hipStream_t st) {
+  if (hipError_t e = pace<ANS, WARM>(a, grid.x)) return e;
+  hipLaunchKernelGGL((energy_direct_d4_kernel<ANS, WARM>), grid, dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
 hipError_t launch_energy_direct_d4(const LaneArgs& a, hipStream_t st) {
   if (a.B <= 0) return hipSuccess;
-  const dim3 grid((unsigned)((a.B + 15) / 16)), block(64);
+  const dim3 grid((unsigned)((a.B + 15) / 16));
   const bool warm = a.r_in != nullptr;
-  if (a.ans_params == nullptr) {
-    if (warm) hipLaunchKernelGGL((energy_direct_d4_kernel<-1, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((energy_direct_d4_kernel<-1, false>), grid, block, 0, st, a);
-  } else if (warm) {
-    switch (a.ans_kind) {
-      case QMPS_ANSATZ_SHALLOW_CNOT: hipLaunchKernelGGL((energy_direct_d4_kernel<QMPS_ANSATZ_SHALLOW_CNOT, true>), grid, block, 0, st, a); break;
-      case QMPS_ANSATZ_SHALLOW_QAOA: hipLaunchKernelGGL((energy_direct_d4_kernel<QMPS_ANSATZ_SHALLOW_QAOA, true>), grid, block, 0, st, a); break;
-      case QMPS_ANSATZ_SHALLOW_CNOT3: hipLaunchKernelGGL((energy_direct_d4_kernel<QMPS_ANSATZ_SHALLOW_CNOT3, true>), grid, block, 0, st, a); break;
-      default: return hipErrorInvalidValue;
-    }
-  } else {
-    switch (a.ans_kind) {
-      case QMPS_ANSATZ_SHALLOW_CNOT: hipLaunchKernelGGL((energy_direct_d4_kernel<QMPS_ANSATZ_SHALLOW_CNOT, false>), grid, block, 0, st, a); break;
-      case QMPS_ANSATZ_SHALLOW_QAOA: hipLaunchKernelGGL((energy_direct_d4_kernel<QMPS_ANSATZ_SHALLOW_QAOA, false>), grid, block, 0, st, a); break;
-      case QMPS_ANSATZ_SHALLOW_CNOT3: hipLaunchKernelGGL((energy_direct_d4_kernel<QMPS_ANSATZ_SHALLOW_CNOT3, false>), grid, block, 0, st, a); break;
-      default: return hipErrorInvalidValue;
-    }
+  if (a.ans_params == nullptr) return warm ? launch_direct_d4<-1, true>(a, grid, st) : launch_direct_d4<-1, false>(a, grid, st);
+  switch (a.ans_kind) {
+    case QMPS_ANSATZ_SHALLOW_CNOT:
+      return warm ? launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT, true>(a, grid, st) : launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT, false>(a, grid, st);
+    case QMPS_ANSATZ_SHALLOW_QAOA:
+      return warm ? launch_direct_d4<QMPS_ANSATZ_SHALLOW_QAOA, true>(a, grid, st) : launch_direct_d4<QMPS_ANSATZ_SHALLOW_QAOA, false>(a, grid, st);
+    case QMPS_ANSATZ_SHALLOW_CNOT3:
+      return warm ? launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT3, true>(a, grid, st) : launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT3, false>(a, grid, st);
+    default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 
 }  // namespace qmps

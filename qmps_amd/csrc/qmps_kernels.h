@@ -72,7 +72,22 @@ struct LaneArgs {
   int krylov_after;
   int* kry_counter;
   int only_pending;
+  // energy_direct_d4_kernel, pacing of the two waves of a SIMD by static priority (filled by launch_energy_direct_d4 from the grid and
+  // the resident wave slots of the device; QMPS_WAVE_SLOTS): workgroups from prio_first on start at s_setprio 1 and drop back to 0
+  // behind phase fence prio_until (kPrioSolve).  prio_until = 0: nobody is raised (grids of one generation, QMPS_WAVE_SLOTS=0).
+  int prio_first;
+  int prio_until;
+#ifdef QMPS_WAVE_TIMELINE
+  unsigned long long* timeline;   // nullable [grid][kTimelineWords]: lane 0 of every wave stamps its phases (qmps_wave_timeline)
+#endif
 };
+// the phase fence of energy_direct_d4_kernel at which a raised wave hands its priority back (LaneArgs::prio_until): behind its solve
+enum { kPrioOff = 0, kPrioSolve = 1 };
+// words per wave of the timeline (QMPS_WAVE_TIMELINE builds): block index, HW_ID, XCC_ID | constant-rate clock at entry, behind the
+// tile's barrier, behind build, solve, acceptance (with the fall-back), density, at the end | core clock at entry, at the end | raised
+constexpr int kTimelineWords = 16;
+enum { kTlBlock = 0, kTlHwId = 1, kTlXccId = 2, kTlEntry = 3, kTlTile = 4, kTlBuild = 5, kTlSolve = 6, kTlAccept = 7, kTlDensity = 8,
+       kTlEnd = 9, kTlCycleEntry = 10, kTlCycleEnd = 11, kTlRaised = 12 };
 
 // D = 8 direct fixed-point solve, one wave per evaluation: writes the environments r[B][8][8] (the warm start / result
 // that energy_block_kernel<8, true> then accepts with one power step)
