@@ -206,7 +206,9 @@ int qmps_abi_version(void);
  *      connected two-point functions (structure factors).
  *      qmps_correlator_sums_two_site, the same sums for two-site operators (energy-density structure factors, the energy variance per site).
  *      qmps_string_correlators, the two-point functions with a one-site string between their ends and the string order itself (disorder
- *      parameters, Jordan-Wigner fermion functions). *      Changed later without a bump (same signatures; nothing a caller can detect beforehand, a refusal is an error code):
+ *      parameters, Jordan-Wigner fermion functions).
+ *      qmps_block_entanglement, the reduced density matrices, spectra and entropies of blocks of one to four contiguous sites.
+ *      Changed later without a bump (same signatures; nothing a caller can detect beforehand, a refusal is an error code):
  *      RESIDENT RESULTS (below): the context knows per evaluation slot, not per context, what its buffers hold, and read-backs that used to return
  *      whatever the buffer held now fail with QMPS_ERR_STATE (same signatures).  qmps_get_env, qmps_get_rdm, qmps_energy_only_launch, qmps_correlators,
  *      qmps_entanglement, qmps_correlator_sums: on a window no launch has stored environments for (another window had them), and after a
@@ -461,6 +463,30 @@ int qmps_string_correlators(qmps_ctx* ctx, int64_t B, int n_ops, const double* o
  * as they are. */
 int qmps_entanglement(qmps_ctx* ctx, int64_t B, double* p_out /* [B][D] */, double* S_out /* nullable, [B] */,
                       double* V_out /* nullable, [B][D][D] complex128 */);
+/* Reduced density matrices, spectra and entropies of blocks of n_sites = 1 .. 4 contiguous sites of the resident states
+ * [window, window + B) with their resident environments (nothing is solved):
+ *   B_t             = A_t1 A_t2 ... A_tn,   t = sum_k t_k 2^(n-k)   (t1 the LEFT site, most significant: the index order of h)
+ *   rho_out[b][t][s] = tr(B_t r B_s^+) / tr r                        (2^n x 2^n complex128; n = 2 is the formula of qmps_get_rdm)
+ *   p_out[b][k]     = k-th largest eigenvalue of herm(rho_b) / tr rho_b, k = 0 .. 2^n - 1  (descending, signed, as in qmps_entanglement)
+ *   S_out[b]        = - sum_(p > 0) p ln p                           (the block entropy S(n) in nats)
+ * tr(O rho) is the expectation of an n-site operator O[t][s] = <t|O|s>; 2 S(1) - S(2) is the mutual information of neighbouring
+ * sites; S(n) tends to twice the half-chain entropy of qmps_entanglement as the block outgrows the correlation length.  The left
+ * environment is taken to be the identity, as in qmps_get_rdm and qmps_correlators: for tensors that are not left isometries the
+ * formula above is still what is computed.  The status of the solve that produced r is not consulted (qmps_get_status).  An
+ * evaluation whose tr r is zero or not finite yields NaN in all of its outputs and leaves its neighbours alone; one whose rho holds a
+ * non-finite element or has zero trace yields NaN in p and S (the rule of qmps_entanglement, whose Jacobi kernels diagonalise rho at
+ * the order 2^n with its sweep caps - four sites are the limit because 16 is its largest order).
+ * QMPS_ERR_ARG, before anything else is looked at, when n_sites is outside [1, 4] or all three outputs are NULL; then the checks of
+ * qmps_correlators: the window, the size limit - the device-side rho, B * 4^n * 16 bytes, may not exceed 1 GiB whether or not rho_out
+ * is given - and QMPS_ERR_STATE when the window runs past the resident states or no environment is resident (also after a launch with
+ * QMPS_FLAG_NO_ENV_OUT).  A refused call writes and allocates nothing; B = 0 writes nothing.  Any of the outputs may be NULL.
+ * One launch of the density-matrix kernel (the one qmps_kernel_time reports) and, when p_out or S_out is given, one of the Jacobi
+ * kernel without eigenvectors; synchronous, with one synchronisation at the read-back.  Resident states, parameters, environments,
+ * energies, iteration counts and statuses stay exactly as they are. */
+int qmps_block_entanglement(qmps_ctx* ctx, int64_t B, int n_sites,
+                            double* rho_out /* nullable, [B][2^n][2^n] complex128 */,
+                            double* p_out   /* nullable, [B][2^n] */,
+                            double* S_out   /* nullable, [B] */);
 
 /* Correlator sums of the resident states [window, window + B) with their resident environments (nothing is solved) - the n >= 1 half
  * of a structure factor, summed to infinity by one linear solve per (state, z) instead of a truncated chain of qmps_correlators.

@@ -97,6 +97,7 @@ SIGNATURES = {
     'qmps_correlators': (c_int, [c_void_p, c_int64, c_int, _dp, c_int, _dp, _dp]),
     'qmps_string_correlators': (c_int, [c_void_p, c_int64, c_int, _dp, _dp, c_int, _dp, _dp, _dp]),
     'qmps_entanglement': (c_int, [c_void_p, c_int64, _dp, _dp, _dp]),
+    'qmps_block_entanglement': (c_int, [c_void_p, c_int64, c_int, _dp, _dp, _dp]),
     'qmps_correlator_sums': (c_int, [c_void_p, c_int64, c_int, _dp, c_int, _dp, _dp, _dp, _dp]),
     'qmps_correlator_sums_two_site': (c_int, [c_void_p, c_int64, c_int, _dp, c_int, _dp, _dp, _dp, _dp]),
     'qmps_energy_batch': (c_int, [c_void_p, c_int64, _dp, c_int, _dp, c_int, _dp, c_int, c_double, _dp, _ip, _ip]),

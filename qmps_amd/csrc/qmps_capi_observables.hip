@@ -1,5 +1,5 @@
 // qmps_capi_observables.hip - C-ABI of the observables of the resident states: two-point functions and string order (kernels: qmps_correlator.hip),
-// Schmidt spectra and entropies (qmps_entanglement.hip), correlator sums of one-site and of two-site operators (qmps_corrsum.hip and the kernel files it dispatches to).  Every call checks its own arguments,
+// Schmidt spectra and entropies (qmps_entanglement.hip), density matrices and entropies of blocks of sites (qmps_block_rdm.hip, then the Jacobi kernels of qmps_entanglement.hip: the one call with two launches), correlator sums of one-site and of two-site operators (qmps_corrsum.hip and the kernel files it dispatches to).  Every call checks its own arguments,
 // passes the shared front, carves its regions out of the scratch buffer, uploads its inputs, launches ONE kernel, reads its results
 // back and synchronises ONE time.  A refused call writes nothing and allocates nothing.
 #include "qmps_ctx.h"
@@ -205,6 +205,48 @@ int qmps_entanglement(qmps_ctx* c, int64_t B, double* p_out, double* S_out, doub
   HIP_TRY(hipMemcpyAsync(p_out, d_p, p_bytes, hipMemcpyDeviceToHost, c->stream));
   if (S_out) HIP_TRY(hipMemcpyAsync(S_out, d_S, S_bytes, hipMemcpyDeviceToHost, c->stream));
   if (V_out) HIP_TRY(hipMemcpyAsync(V_out, d_V, V_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return QMPS_OK;
+}
+QMPS_API_CATCH
+
+int qmps_block_entanglement(qmps_ctx* c, int64_t B, int n_sites, double* rho_out, double* p_out, double* S_out) try {
+  if (n_sites < 1 || n_sites > qmps::kMaxBlockSites)
+    return fail(QMPS_ERR_ARG, "n_sites=%d outside [1, %d] (the spectrum of a larger block is no Jacobi order of this library)", n_sites, qmps::kMaxBlockSites);
+  if (!rho_out && !p_out && !S_out) return fail(QMPS_ERR_ARG, "null rho_out, p_out and S_out: nothing to return");
+  if (!c) return fail(QMPS_ERR_ARG, "null context");
+  const int T = 1 << n_sites;
+  const uint64_t per_eval = (uint64_t)T * T * 16;                   // the device-side rho, whether or not it is read back
+  bool empty = false;
+  if (int rc = resident_front(c, B, per_eval, "n_sites", empty)) return rc;
+  if (empty) return QMPS_OK;
+  if (int rc = ensure_tensors(c)) return rc;
+  const bool spectrum = p_out || S_out;
+  const size_t rho_bytes = (size_t)B * per_eval, p_bytes = spectrum ? (size_t)B * T * 8 : 0, S_bytes = spectrum ? (size_t)B * 8 : 0;
+  ScratchLayout s;
+  const size_t rho_at = s.take(rho_bytes), p_at = s.take(p_bytes), S_at = s.take(S_bytes);
+  if (int rc = ensure_scratch(c, s.bytes)) return rc;
+  char* base = (char*)c->d_scratch;
+  char *d_rho = base + rho_at, *d_p = base + p_at, *d_S = base + S_at;
+  qmps::BlockRdmArgs a{};
+  a.A = win_A(c);
+  a.r = win_r(c);
+  a.rho = d_rho;
+  a.B = B;
+  a.n_sites = n_sites;
+  if (int rc = timed_launch(c, "block_rdm", qmps::launch_block_rdm, a)) return rc;
+  if (spectrum) {
+    // the Jacobi kernels of qmps_entanglement at the order 2^n, on rho where it lies: herm(rho) / tr rho, its rule for NaN
+    qmps::EntanglementArgs j{};
+    j.r = d_rho;
+    j.p = (double*)d_p;
+    j.S = (double*)d_S;
+    j.B = B;
+    HIP_TRY(qmps::launch_entanglement(T, j, c->stream));
+  }
+  if (rho_out) HIP_TRY(hipMemcpyAsync(rho_out, d_rho, rho_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (p_out) HIP_TRY(hipMemcpyAsync(p_out, d_p, p_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (S_out) HIP_TRY(hipMemcpyAsync(S_out, d_S, S_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return QMPS_OK;
 }

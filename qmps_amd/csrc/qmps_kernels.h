@@ -487,6 +487,17 @@ struct EntanglementArgs {
   int64_t B;
 };
 hipError_t launch_entanglement(int D, const EntanglementArgs& a, hipStream_t st);
+// reduced density matrices of n contiguous sites (qmps_block_rdm.hip): one launch whatever n is; their spectra are launch_entanglement
+// at the order 2^n, which is why four sites are the limit
+constexpr int kMaxBlockSites = 4;
+struct BlockRdmArgs {
+  const void* A;       // [B][2][D][D] complex
+  const void* r;       // [B][D][D] complex right environments (any normalisation: rho is divided by tr r)
+  void* rho;           // [B][2^n][2^n] complex: rho[t][s] = tr(B_t r B_s^+) / tr r, t = sum_k t_k 2^(n-k) with t_1 the left site
+  int64_t B;
+  int n_sites;         // 1 <= n <= kMaxBlockSites
+};
+hipError_t launch_block_rdm(int D, const BlockRdmArgs& a, hipStream_t st);
 // correlator sums (dispatch: qmps_corrsum.hip; kernels: qmps_corrsum_small.hip, qmps_corrsum_block.hip): one dense solve of order D^2 per (evaluation, z), one launch
 struct CorrSumArgs {
   const void* A;       // [B][2][D][D] complex

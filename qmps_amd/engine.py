@@ -274,7 +274,12 @@ class EnergyEngine:
         L.check(self._lib.qmps_get_env(self._ctx, B, _f64(r.view(np.float64))))
         return r
 
-    def rdm(self, B=None):
+    def rdm(self, B=None, n_sites=None):
+        """Two-site reduced density matrices (B, 4, 4) of the energy launch over the window (qmps_get_rdm: an energy-only launch on the
+        resident environments).  n_sites = 1 .. 4: the density matrices of that many sites from `block_rdm` instead, (B, 2^n, 2^n),
+        which touch no energies."""
+        if n_sites is not None:
+            return self.block_rdm(n_sites, B)
         B = self.B if B is None else B
         rho = np.empty((B, 4, 4), dtype=np.complex128)
         L.check(self._lib.qmps_get_rdm(self._ctx, B, _f64(rho.view(np.float64))))
@@ -397,6 +402,51 @@ class EnergyEngine:
         V = np.empty((n, self.D, self.D), dtype=np.complex128) if want_vectors else None
         L.check(self._lib.qmps_entanglement(self._ctx, B, _f64(p), _f64(S), None if V is None else _f64(V.view(np.float64))))
         return (p, S, V) if want_vectors else (p, S)
+
+    def _block(self, n_sites, B, want_rdm, want_spectrum):
+        """One call of qmps_block_entanglement: (rho or None, p or None, S or None).  The library checks n_sites and the sizes before
+        anything is written: for arguments it refuses the arrays are empty and never touched."""
+        B = self.B if B is None else int(B)
+        n_sites = int(n_sites)
+        fits = 1 <= n_sites <= 4 and 0 <= B <= (1 << 26) >> (2 * n_sites)
+        n, T = (B, 1 << n_sites) if fits else (0, 0)
+        rho = np.empty((n, T, T), dtype=np.complex128) if want_rdm else None
+        p = np.empty((n, T)) if want_spectrum else None
+        S = np.empty(n) if want_spectrum else None
+        L.check(self._lib.qmps_block_entanglement(self._ctx, B, n_sites, None if rho is None else _f64(rho.view(np.float64)),
+                                                  None if p is None else _f64(p), None if S is None else _f64(S)))
+        return rho, p, S
+
+    def block_rdm(self, n_sites, B=None):
+        """Reduced density matrices of n_sites = 1 .. 4 contiguous sites of the resident states with their resident environments
+        (`launch` with the environments stored, or `set_env_guess`; nothing is solved here): rho[b, t, s] = tr(B_t r B_s^+) / tr r with
+        B_t = A_t1 .. A_tn and t = sum_k t_k 2^(n-k), the left site most significant (the index order of `set_hamiltonian`); shape
+        (B, 2^n, 2^n) complex128.  n_sites = 2 is the formula of `rdm`, which needs an energy launch; this needs none.  An r whose trace
+        is zero or not finite gives NaN.  One kernel launch, one synchronisation."""
+        return self._block(n_sites, B, True, False)[0]
+
+    def block_entanglement(self, n_sites, B=None, want_rdm=False):
+        """Spectra and entropies of blocks of n_sites = 1 .. 4 contiguous sites: p[b, k] = k-th largest eigenvalue of
+        herm(rho_b) / tr rho_b with rho of `block_rdm`, shape (B, 2^n), descending and signed, and the block entropy
+        S[b] = - sum_(p > 0) p ln p in nats, shape (B,).  want_rdm=True: returns (p, S, rho).  2 S(1) - S(2) is the mutual information
+        of neighbouring sites; S(n) tends to twice the half-chain entropy of `entanglement` as the block outgrows the correlation
+        length.  Two kernel launches (the density matrices, then the Jacobi eigensolver of `entanglement` at the order 2^n), one
+        synchronisation."""
+        rho, p, S = self._block(n_sites, B, want_rdm, True)
+        return (p, S, rho) if want_rdm else (p, S)
+
+    def expectation(self, ops, B=None):
+        """Expectation values of operators on n = 1 .. 4 contiguous sites: ops of shape (m, 2^n, 2^n) or one (2^n, 2^n) matrix,
+        O[t, s] = <t|O|s> in the index order of `set_hamiltonian` (left site most significant), not necessarily Hermitian.  Returns
+        (B, m) complex128, tr(O_a rho_b) with rho of `block_rdm` - one kernel launch, the traces on the host."""
+        ops = np.asarray(ops, dtype=np.complex128)
+        if ops.ndim == 2:
+            ops = ops[None]
+        n_sites = {2: 1, 4: 2, 8: 3, 16: 4}.get(ops.shape[-1]) if ops.ndim == 3 and ops.shape[-1] == ops.shape[-2] else None
+        if n_sites is None:
+            raise ValueError(f'ops: expected shape (m, 2^n, 2^n) or (2^n, 2^n) with n in 1 .. 4, got {ops.shape}')
+        rho = self.block_rdm(n_sites, B)
+        return np.einsum('ats,bst->ba', ops, rho)
 
     def summed_cost(self, B=None):
         cost = np.empty(max(self.n_terms, 1))

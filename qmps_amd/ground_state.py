@@ -475,6 +475,30 @@ def entanglement_entropy(params, D=2, state_tensor=ShallowCNOTStateTensor):
     return S, p, eng.results_status(K)
 
 
+def block_entropy(params, n_sites, D=2, state_tensor=ShallowCNOTStateTensor):
+    """Entanglement of a block of n_sites = 1 .. 4 contiguous sites with the rest of the chain, for the states of K parameter rows - the
+    companion of `entanglement_entropy`, whose cut has one end where the block has two:
+      S (K,)          von Neumann entropy of the block in nats, at most min(n ln 2, 2 ln D); it tends to twice the half-chain entropy as
+                      the block outgrows the correlation length
+      p (K, 2^n)      the spectrum of the block's reduced density matrix, descending
+      status (K,)     of the environment solve (STATUS_OK = 0; the values of any other row are not to be trusted)
+    2 S(1) - S(2) is the mutual information of neighbouring sites.  One environment solve with the environments stored, one launch of
+    the block density-matrix kernel and one of the Jacobi kernel (`EnergyEngine.block_entanglement`)."""
+    eng, K = _resident_states(params, D, state_tensor)
+    p, S = eng.block_entanglement(n_sites, B=K)
+    return S, p, eng.results_status(K)
+
+
+def local_expectation(params, ops, D=2, state_tensor=ShallowCNOTStateTensor):
+    """Expectation values of operators on n = 1 .. 4 contiguous sites in the states of K parameter rows:
+      values (K, m)   tr(O_a rho_n), complex
+      status (K,)     of the environment solve (STATUS_OK = 0; the values of any other row are not to be trusted)
+    ops: (m, 2^n, 2^n) or one (2^n, 2^n) matrix, O[t, s] = <t|O|s> with the left site most significant (np.kron(Z, np.kron(X, Z)) is the
+    cluster term on three sites), not necessarily Hermitian (`EnergyEngine.expectation`)."""
+    eng, K = _resident_states(params, D, state_tensor)
+    return eng.expectation(ops, B=K), eng.results_status(K)
+
+
 def structure_factor(params, ops, k, D=2, state_tensor=ShallowCNOTStateTensor):
     """Static structure factors of the states of K parameter rows - the companion of `ground_state_sweep` (params = out['params']) and
     `correlation_functions`:
