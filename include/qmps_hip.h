@@ -171,7 +171,13 @@ extern "C" {
  *                         one generation of resident waves the last half generation starts at s_setprio 1 and hands the priority back behind
  *                         its solve (same arithmetic, same results bit for bit).  0 switches pacing off; a positive value stands for the
  *                         number of resident wave slots, which otherwise comes from the occupancy of the kernel times the CU count (the
- *                         tests set 4, so that a handful of workgroups crosses every branch).  Read on every launch.
+ *                         tests set 4, so that a handful of workgroups crosses every branch).  Read on every launch.  Launches on the
+ *                         launch lanes (below) are paced only when the variable is set.
+ *   QMPS_LAUNCH_LANES     D = 4, QMPS_ENV_DIRECT: consecutive qmps_energy_launch calls alternate between two compute streams of the context
+ *                         (2, the default), so that the first waves of a launch take the SIMD slots its predecessor's last waves leave; a
+ *                         launch waits for the earlier ones whose windows or cost-accumulator positions it shares, and every other call
+ *                         runs behind both streams, so results, timers and read-backs are those of one stream, bit for bit.  1: every launch
+ *                         on the context stream.  Read by qmps_create.
  * Everything else that used to be tunable from the environment (thresholds, schedules: profiles/EXPERIMENTS.md) is compiled
  * in only with -DQMPS_DEBUG_KNOBS; the shipped library ignores those variables (tests/test_cabi.py checks both lists). */
 

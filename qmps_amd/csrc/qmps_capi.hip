@@ -1,5 +1,6 @@
 // qmps_capi.hip - the context of the C-ABI of libqmps_hip.so (declared in include/qmps_hip.h): the error string, library / device
-// queries, the qmps_host helpers behind qmps_ctx.h, context lifetime (one device + one HIP stream + HBM buffers + pinned staging),
+// queries, the qmps_host helpers behind qmps_ctx.h (bind and the launch lanes among them), context lifetime (one device + one HIP stream
+// + HBM buffers + pinned staging),
 // the state, Hamiltonian, window and guess setters, the solver / handoff / roto-rule / timing-period settings, timers.
 // The energy path and read-back: qmps_capi_energy.hip; the summed-cost exchange (RCCL): qmps_capi_cost.hip; the brick-wall calls:
 // qmps_capi_brickwall.hip; the peak probes: qmps_capi_probe.hip; the time-evolution overlap objective: qmps_capi_overlap.hip; the
@@ -23,9 +24,66 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-int bind(qmps_ctx* c) {
+int bind_device(qmps_ctx* c) {
   if (!c) return fail(QMPS_ERR_ARG, "null context");
   HIP_TRY(hipSetDevice(c->device));
+  return QMPS_OK;
+}
+
+int bind(qmps_ctx* c) {
+  if (int rc = bind_device(c)) return rc;
+  return join_lanes(c);
+}
+
+// The launch lanes (qmps_ctx.h, qmps_hazard.h).  Waiting for an event that has completed puts nothing on the stream.
+int lane_wait(qmps_ctx* c, hipStream_t waiter, int lane, int64_t seq) {
+  if (seq < 1) return QMPS_OK;
+  if (c->lane_table.kept(lane, seq)) {
+    HIP_TRY(hipStreamWaitEvent(waiter, c->lane_ev[lane][LaneTable::slot_of(seq)], 0));
+  } else {      // its event has been taken over by a later launch of the lane: wait for the lane as it stands
+    HIP_TRY(hipEventRecord(c->lane_fork, c->lane(lane)));
+    HIP_TRY(hipStreamWaitEvent(waiter, c->lane_fork, 0));
+  }
+  return QMPS_OK;
+}
+
+namespace {
+// what lanes_begin / lanes_join (qmps_hazard.h) ask for, on the context's streams
+struct LaneIO {
+  qmps_ctx* c;
+  int wait(int waiter, int lane, int64_t seq) { return lane_wait(c, c->lane(waiter), lane, seq); }
+  int fork() {
+    HIP_TRY(hipEventRecord(c->lane_fork, c->stream));
+    HIP_TRY(hipStreamWaitEvent(c->lane_stream, c->lane_fork, 0));
+    return QMPS_OK;
+  }
+};
+}  // namespace
+
+int join_lanes(qmps_ctx* c) {
+  if (c->capturing) return QMPS_OK;      // (the drivers that capture have bound, and issue no lane launches)
+  LaneIO io{c};
+  return lanes_join(c->lane_table, io, c->main_touched);
+}
+
+int lane_begin(qmps_ctx* c, const LaunchFootprint& f, int* lane_out) {
+  if (!c->lane_stream) {
+    HIP_TRY(hipStreamCreateWithFlags(&c->lane_stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&c->lane_fork, hipEventDisableTiming));
+    for (auto& lane : c->lane_ev)
+      for (hipEvent_t& e : lane) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  const int lane = c->next_lane;
+  c->next_lane = 1 - lane;
+  LaneIO io{c};
+  if (int rc = lanes_begin(c->lane_table, io, lane, f, c->main_touched)) return rc;
+  *lane_out = lane;
+  return QMPS_OK;
+}
+
+int lane_end(qmps_ctx* c, const LaunchFootprint& f, int lane, int64_t* seq) {
+  *seq = c->lane_table.record(lane, f);
+  HIP_TRY(hipEventRecord(c->lane_ev[lane][LaneTable::slot_of(*seq)], c->lane(lane)));
   return QMPS_OK;
 }
 
@@ -171,6 +229,8 @@ int qmps_create(int device, int D, int64_t max_batch, qmps_ctx** out) try {
   int rc = [&]() -> int {
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    c->launch_stream = c->stream;
+    c->lanes = qmps::launch_lanes();
     HIP_TRY(hipEventCreate(&c->ev0));
     HIP_TRY(hipEventCreate(&c->ev1));
     for (int i = 0; i < qmps_ctx::kRing; ++i) {
@@ -236,6 +296,7 @@ int qmps_destroy(qmps_ctx* c) try {
   c->lockstep.clear();
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->lane_stream) (void)hipStreamSynchronize(c->lane_stream);
   if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
   if (c->comm_stream2) (void)hipStreamSynchronize(c->comm_stream2);
   if (c->roto_exec) (void)hipGraphExecDestroy(c->roto_exec);
@@ -271,6 +332,11 @@ int qmps_destroy(qmps_ctx* c) try {
     if (c->kev0[i]) (void)hipEventDestroy(c->kev0[i]);
     if (c->kev1[i]) (void)hipEventDestroy(c->kev1[i]);
   }
+  for (auto& lane : c->lane_ev)
+    for (hipEvent_t e : lane)
+      if (e) (void)hipEventDestroy(e);
+  if (c->lane_fork) (void)hipEventDestroy(c->lane_fork);
+  if (c->lane_stream) (void)hipStreamDestroy(c->lane_stream);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return QMPS_OK;
@@ -280,7 +346,7 @@ QMPS_API_CATCH
 int qmps_sync(qmps_ctx* c) try {
   if (int rc = bind(c)) return rc;
   if (int rc = close_group(c)) return rc;     // costs still waiting for their exchange go out now
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));      // (behind lane 1 since bind)
   HIP_TRY(hipStreamSynchronize(c->comm_stream));
   HIP_TRY(hipStreamSynchronize(c->comm_stream2));
   return QMPS_OK;
@@ -546,6 +612,8 @@ int qmps_kernel_time(qmps_ctx* c, int n_last, float* avg_ms, char* name, int nam
 }
 QMPS_API_CATCH
 
+// Both events stand on the context stream behind a join of the lanes (bind), and lane 1 starts nothing new before the first of them
+// (main_touched): the interval covers the work of both lanes issued between the two calls, and none from before.
 int qmps_timer_begin(qmps_ctx* c) try {
   if (int rc = bind(c)) return rc;
   HIP_TRY(hipEventRecord(c->ev0, c->stream));

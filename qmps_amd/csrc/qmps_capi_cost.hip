@@ -24,10 +24,11 @@ int setup_accumulator(qmps_ctx* c, qmps::LaneArgs& a, int64_t B, int64_t adds, i
   const int slot = (int)(c->groups % qmps_ctx::kCostSlots), pos = c->group_fill;
   const int nslot = (int)((c->groups + 2) % qmps_ctx::kCostSlots), npos = pos;
   c->acc_after_event[slot][pos] = false;
+  c->acc_seq[slot][pos] = 0;      // (a launch on the lanes enters itself behind this call: energy_direct_d4)
   if (c->acc_dirty[slot][pos]) {
     // unusual call order (exchange period changed, a partly filled group, an accumulated cost that was dropped): clear
-    // it now on the compute stream, and order this position's finish kernel behind that by an event
-    HIP_TRY(hipMemsetAsync(c->acc_at(slot, pos), 0, qmps::kAccWords * sizeof(long long), c->stream));
+    // it now on the launch's stream, and order this position's finish kernel behind that by an event
+    HIP_TRY(hipMemsetAsync(c->acc_at(slot, pos), 0, qmps::kAccWords * sizeof(long long), c->launch_stream));
     c->acc_dirty[slot][pos] = false;
     c->acc_after_event[slot][pos] = true;
   }
@@ -90,15 +91,20 @@ int close_group(qmps_ctx* c) {
     constexpr bool dbg_noevent = false, dbg_noar = false, dbg_nofinish = false, dbg_nopoll = false;
 #endif
     // positions whose cost lives in a fixed-point accumulator need no ordering on the compute stream: their finish
-    // kernel polls the arrival counts.  Only costs written by reduction kernels on the compute stream need the event.
+    // kernel polls the arrival counts.  Only costs written by reduction kernels on the compute stream need the event - and an
+    // accumulator that a memset in front of its launch cleared, unless that launch went to a lane: the finish kernel of such a
+    // position waits for the launch's own event, on whichever lane it ran (nothing is put on a compute stream for it).
     bool need_event = false;
-    for (int pos = 0; pos < c->group_fill; ++pos) need_event = need_event || !c->acc_is[slot][pos] || c->acc_after_event[slot][pos];
+    for (int pos = 0; pos < c->group_fill; ++pos)
+      need_event = need_event || !c->acc_is[slot][pos] || (c->acc_after_event[slot][pos] && c->acc_seq[slot][pos] == 0);
     if (need_event && !dbg_noevent) {
       HIP_TRY(hipEventRecord(c->cost_ready[slot], c->stream));
       HIP_TRY(hipStreamWaitEvent(c->comm_stream_of(slot), c->cost_ready[slot], 0));
     }
     for (int pos = 0; pos < c->group_fill; ++pos)
       if (c->acc_is[slot][pos]) {   // fixed-point accumulators -> doubles, off the compute stream
+        if (c->acc_seq[slot][pos] > 0 && !dbg_noevent)
+          if (int rc = lane_wait(c, c->comm_stream_of(slot), c->acc_lane[slot][pos], c->acc_seq[slot][pos])) return rc;
         if (!dbg_nofinish)
           HIP_TRY(qmps::launch_cost_finish(c->acc_at(slot, pos), c->acc_shards[slot][pos], c->acc_expect[slot][pos], dbg_nopoll ? 0 : 1 << 22,
                                            1.0 / c->acc_scale[slot][pos], c->n_terms, base + (size_t)pos * kMaxTerms,
@@ -243,7 +249,7 @@ int qmps_set_exchange_period(qmps_ctx* c, int steps) try {
 QMPS_API_CATCH
 
 int qmps_cost_launch(qmps_ctx* c, int64_t B) try {
-  if (int rc = bind(c)) return rc;
+  if (int rc = bind_device(c)) return rc;
   if (int rc = check_window(c, B)) return rc;
   if (c->n_terms < 1) return fail(QMPS_ERR_STATE, "no energies resident");
   // device-side sum into this step's place in the current group of the ring (main stream) ...
@@ -254,6 +260,10 @@ int qmps_cost_launch(qmps_ctx* c, int64_t B) try {
   // A slot is reused only after its previous all-reduce has finished.  Costs written by a reduction kernel on the compute
   // stream need that as a stream dependency; a cost that lives in a fixed-point accumulator is converted on the slot's own
   // communication stream, behind that all-reduce, and puts nothing on the compute stream (no barrier packet per step).
+  // A cost the energy kernel summed itself puts nothing on the context stream and reads nothing: the lanes stay apart (close_group
+  // orders the finish kernel behind the launch).  A reduction kernel reads E or the partial sums behind both lanes.
+  if (!in_kernel)
+    if (int rc = join_lanes(c)) return rc;
   if (c->comm && !in_kernel && c->groups >= qmps_ctx::kCostSlots && !c->slot_waited) {
     HIP_TRY(hipStreamWaitEvent(c->stream, c->cost_reduced[slot], 0));
     c->slot_waited = true;

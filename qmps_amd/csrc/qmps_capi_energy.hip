@@ -1,8 +1,8 @@
 // qmps_capi_energy.hip - the energy path of the C-ABI (declared in include/qmps_hip.h): qmps_energy_launch with a function per solver
 // path and their dispatcher, the energy-only pass, read-back (energies, status, environments, density matrices), the one-shot batch
-// calls and the two-site unit cell.  Asynchronous launches on the context stream; the setters they follow and the shared helpers:
-// qmps_capi.hip, qmps_ctx.h.  Where an accumulated cost goes (setup_accumulator, qmps_cost_launch): qmps_capi_cost.hip.  The
-// rotosolve drivers built on these launches: qmps_capi_roto.hip.
+// calls and the two-site unit cell.  Asynchronous launches on the context stream - the fused D = 4 direct kernel alternately on the two
+// launch lanes (qmps_hazard.h); the setters they follow and the shared helpers: qmps_capi.hip, qmps_ctx.h.  Where an accumulated cost
+// goes (setup_accumulator, qmps_cost_launch): qmps_capi_cost.hip.  The rotosolve drivers built on these launches: qmps_capi_roto.hip.
 #include "qmps_ctx.h"
 #include "qmps_direct_core.h"
 
@@ -73,18 +73,38 @@ int power_with_krylov(qmps_ctx* c, qmps::LaneArgs& a, bool krylov, hipError_t (*
 // D = 4: direct fixed-point solve + acceptance power step + energies in ONE kernel (a DPP quad per evaluation); one read of A, one
 // store of E (and, unless switched off, of r) per evaluation.  a.r_in (qmps_set_env_guess / QMPS_FLAG_WARM_RESIDENT): evaluations
 // whose guess passes the acceptance test skip the solve.
-int energy_direct_d4(qmps_ctx* c, qmps::LaneArgs& a, int flags, KernelTimer& t) {
+// on_lanes (qmps_energy_launch decides): the launch goes to the next of the two compute lanes, behind the launches of the other lane
+// that its footprint conflicts with (qmps_hazard.h) - before anything of it, the clearing memset of setup_accumulator included,
+// touches memory.  The event pair of a timed launch stands on the launch's own lane, so it may span waves of a neighbour.
+int energy_direct_d4(qmps_ctx* c, qmps::LaneArgs& a, int flags, KernelTimer& t, bool on_lanes) {
   a.r_out = (flags & QMPS_FLAG_NO_ENV_OUT) ? nullptr : win_r(c);
-  if (int rc = cost_sink(c, a, flags & QMPS_FLAG_ACCUMULATE_COST, (a.B + 15) / 16, 16)) return rc;
+  const bool accumulate = (flags & QMPS_FLAG_ACCUMULATE_COST) != 0;
+  LaunchFootprint f;
+  int lane = 0;
+  if (on_lanes) {
+    f.lo = c->window; f.hi = c->window + a.B;
+    f.acc = accumulate ? acc_position(c, 0) : -1;
+    f.acc_zero = accumulate ? acc_position(c, 2) : -1;      // (whether or not this launch finds it dirty)
+    f.partials = !accumulate;
+    if (int rc = lane_begin(c, f, &lane)) return rc;
+  }
+  Restore<hipStream_t> on_lane(c->launch_stream, c->lane(lane));
+  if (int rc = cost_sink(c, a, accumulate, (a.B + 15) / 16, 16)) return rc;
   c->dominant = "energy_direct_d4_kernel";
 #ifdef QMPS_WAVE_TIMELINE
   a.timeline = c->d_timeline;
 #endif
   HIP_TRY(t.start());
-  HIP_TRY(qmps::launch_energy_direct_d4(a, c->stream));
+  HIP_TRY(qmps::launch_energy_direct_d4(a, c->launch_stream, on_lanes));
   HIP_TRY(t.stop());
+  if (on_lanes) {
+    int64_t seq = 0;
+    if (int rc = lane_end(c, f, lane, &seq)) return rc;
+    if (accumulate) { c->acc_lane[c->acc_slot][c->acc_pos] = lane; c->acc_seq[c->acc_slot][c->acc_pos] = seq; }
+  }
   return QMPS_OK;
 }
+int energy_direct_d4_serial(qmps_ctx* c, qmps::LaneArgs& a, int flags, KernelTimer& t) { return energy_direct_d4(c, a, flags, t, false); }
 
 // D = 16: power iteration on the matrix cores (one wave per evaluation) with the Krylov fall-back (QMPS_NO_KRYLOV: power iteration
 // alone), then the energy pass
@@ -226,7 +246,7 @@ int energy_squaring_d4(qmps_ctx* c, qmps::LaneArgs& a, int, KernelTimer& t) {
 // solver: QMPS_ENV_DIRECT only at D = 4 (elsewhere already rewritten to QMPS_ENV_POWER_SQUARING).  The documented switches are
 // read on every launch: the tests flip them between the launches of one context.
 EnergyPathFn energy_path(const qmps_ctx* c, int solver, int max_iter) {
-  if (solver == QMPS_ENV_DIRECT) return energy_direct_d4;
+  if (solver == QMPS_ENV_DIRECT) return energy_direct_d4_serial;
   if (c->D == 16 && !documented_switch("QMPS_D16_BLOCK")) return energy_mfma_d16;
   const bool hybrid = solver == QMPS_ENV_POWER_SQUARING && c->D <= 4 && c->handoff < max_iter;
   if (hybrid) return c->D == 2 ? energy_squaring_d2 : energy_squaring_d4;
@@ -237,8 +257,13 @@ EnergyPathFn energy_path(const qmps_ctx* c, int solver, int max_iter) {
 
 }  // namespace
 
-int qmps_energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int flags) try {
-  if (int rc = bind(c)) return rc;
+int qmps_host::energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int flags, bool may_overlap) {
+  if (int rc = bind_device(c)) return rc;
+  // The fused D = 4 direct kernel alternates between the two lanes and orders itself by its footprint; every other path, a launch
+  // inside a graph capture and a launch that stamps a wave timeline stay on the context stream, behind both lanes like any other call.
+  const bool on_lanes = may_overlap && c->lanes > 1 && c->D == 4 && (flags & 0xff) == QMPS_ENV_DIRECT && !c->capturing && c->d_timeline == nullptr && B > 0;
+  if (!on_lanes)
+    if (int rc = join_lanes(c)) return rc;
   if (int rc = check_window(c, B)) return rc;
   if (int rc = check_resident(c, B)) return rc;
   if (c->n_terms < 1) return fail(QMPS_ERR_STATE, "qmps_set_hamiltonian has not been called");
@@ -266,8 +291,11 @@ int qmps_energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int fla
   c->grad_warm_T = 0;
   const ResidentStates& s = c->states;
   const bool fused = direct && s.ansatz && fusable_ansatz(c, s.kind);   // the direct kernel builds the tensors itself
-  if (!fused)
+  if (!fused) {
+    if (on_lanes && !s.has_tensors)      // the tensor build writes d_A on the context stream
+      if (int rc = join_lanes(c)) return rc;
     if (int rc = ensure_tensors(c)) return rc;
+  }
   qmps::LaneArgs a = make_args(c, B, max_iter, tol, true);
   // (a window none of whose slots was ever stored or guessed starts cold, as documented: its part of d_r holds whatever was there)
   if (warm_resident) a.r_in = window_has_start(c, B) ? win_r(c) : nullptr;
@@ -278,7 +306,7 @@ int qmps_energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int fla
   }
   c->partials_B = -1;
   KernelTimer timer(c, periodic_timing(c));
-  if (int rc = run(c, a, flags, timer)) return rc;
+  if (int rc = on_lanes ? energy_direct_d4(c, a, flags, timer, true) : run(c, a, flags, timer)) return rc;
   if (!c->capturing) c->launches++;
   // only the direct D = 4 path may store no environments (QMPS_FLAG_NO_ENV_OUT).  A warm launch that stores nothing leaves what it started
   // from in place: environments an earlier launch stored for these states stay what they were; guesses stay the start of the next solve,
@@ -301,6 +329,10 @@ int qmps_energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int fla
   c->overlap_vals.remove(lo, hi);     // (rounds and statuses of an overlap launch over these slots are gone)
   c->overlap_x.remove(lo, hi);
   return QMPS_OK;
+}
+
+int qmps_energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int flags) try {
+  return energy_launch(c, B, max_iter, tol, flags, true);
 }
 QMPS_API_CATCH
 
@@ -415,7 +447,7 @@ int qmps_energy_batch(qmps_ctx* c, int64_t B, const double* states, int kind, co
   if (int rc = qmps_set_states(c, B, states, kind)) return rc;
   if (int rc = qmps_set_hamiltonian(c, n_terms, h)) return rc;
   if (int rc = qmps_set_env_guess(c, B, r0)) return rc;
-  if (int rc = qmps_energy_launch(c, B, max_iter, tol, c->default_solver | QMPS_FLAG_KRYLOV_FALLBACK)) return rc;
+  if (int rc = energy_launch(c, B, max_iter, tol, c->default_solver | QMPS_FLAG_KRYLOV_FALLBACK, false)) return rc;
   return qmps_get_energies(c, B, E_out, iters_out, status_out);
 }
 QMPS_API_CATCH
@@ -431,7 +463,7 @@ int qmps_energy_batch_ansatz(qmps_ctx* c, int64_t B, int ansatz_kind, int n_para
     Restore<bool> deferred(c->defer_sync, true);
     rc = qmps_set_states_ansatz(c, B, ansatz_kind, n_params, params);
     if (!rc) rc = qmps_set_hamiltonian(c, n_terms, h);
-    if (!rc) rc = qmps_energy_launch(c, B, max_iter, tol, c->default_solver | QMPS_FLAG_KRYLOV_FALLBACK | ((c->D == 4 && c->default_solver == QMPS_ENV_DIRECT) ? QMPS_FLAG_NO_ENV_OUT : 0));
+    if (!rc) rc = energy_launch(c, B, max_iter, tol, c->default_solver | QMPS_FLAG_KRYLOV_FALLBACK | ((c->D == 4 && c->default_solver == QMPS_ENV_DIRECT) ? QMPS_FLAG_NO_ENV_OUT : 0), false);
   }
   if (rc) {
     (void)hipStreamSynchronize(c->stream);
@@ -450,7 +482,7 @@ int qmps_energy_batch_su(qmps_ctx* c, int64_t B, const double* params, const dou
     Restore<bool> deferred(c->defer_sync, true);
     rc = qmps_set_states_su(c, B, params);
     if (!rc) rc = qmps_set_hamiltonian(c, n_terms, h);
-    if (!rc) rc = qmps_energy_launch(c, B, max_iter, tol, c->default_solver | QMPS_FLAG_KRYLOV_FALLBACK);
+    if (!rc) rc = energy_launch(c, B, max_iter, tol, c->default_solver | QMPS_FLAG_KRYLOV_FALLBACK, false);
   }
   if (rc) {
     (void)hipStreamSynchronize(c->stream);
@@ -471,7 +503,7 @@ int qmps_env_batch(qmps_ctx* c, int64_t B, const double* states, int kind, const
     if (int rc = qmps_set_hamiltonian(c, 1, zero)) return rc;
   }
   if (int rc = qmps_set_env_guess(c, B, r0)) return rc;
-  if (int rc = qmps_energy_launch(c, B, max_iter, tol, c->default_solver | QMPS_FLAG_KRYLOV_FALLBACK)) return rc;
+  if (int rc = energy_launch(c, B, max_iter, tol, c->default_solver | QMPS_FLAG_KRYLOV_FALLBACK, false)) return rc;
   if (int rc = qmps_get_energies(c, B, nullptr, iters_out, status_out)) return rc;
   return qmps_get_env(c, B, r_out);
 }

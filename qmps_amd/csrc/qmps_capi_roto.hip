@@ -85,7 +85,7 @@ int whole_run(qmps_ctx* c, const RotoRun& r, hipError_t (*launch)(int, const qmp
   HIP_TRY(qmps::launch_ansatz(c->D, r.kind, r.base, r.P, c->d_A, r.R, c->stream));
   c->states.hold_tensors(r.R);
   forget_results(c);      // the launch below states what the R final vectors leave resident
-  return qmps_energy_launch(c, r.R, r.max_iter, r.tol, c->default_solver);
+  return energy_launch(c, r.R, r.max_iter, r.tol, c->default_solver, false);
 }
 
 // One parameter update = shift build -> ansatz -> environment + energy -> closed-form update; one sweep = n_params updates.  The
@@ -105,7 +105,7 @@ int step_by_step(qmps_ctx* c, const RotoRun& r) {
       HIP_TRY(qmps::launch_ansatz_shifted(c->D, r.kind, r.base, r.P, c->d_A, n, shifts, r.idx, c->stream));
       c->states.hold_tensors(n);
     }
-    return qmps_energy_launch(c, n, r.max_iter, r.tol, c->default_solver);
+    return energy_launch(c, n, r.max_iter, r.tol, c->default_solver, false);
   };
   auto one_sweep = [&]() -> int {
     for (int i = 0; i < r.P; ++i) {

@@ -1,6 +1,7 @@
 // qmps_ctx.h - internal to libqmps_hip.so: the context behind the opaque `qmps_ctx*` of include/qmps_hip.h and the host-side
 // helpers shared by the translation units of the C-ABI:
 //   qmps_capi.hip            error string, context lifetime, states and settings, timers; defines the helpers declared below
+//   qmps_hazard.h            (free of HIP) which launches may overlap on the two launch lanes, and the waits for those that may not
 //   qmps_capi_energy.hip     the energy path, read-back, the one-shot batch calls, the two-site unit cell
 //   qmps_capi_cost.hip       the summed-cost exchange and its RCCL communicator (setup_accumulator, close_group)
 //   qmps_capi_brickwall.hip  the brick-wall calls
@@ -38,6 +39,7 @@
 #include "qmps_hip.h"
 #include "qmps_kernels.h"
 #include "qmps_knobs.h"
+#include "qmps_hazard.h"
 #include "qmps_resident.h"
 
 namespace qmps_host {
@@ -82,6 +84,20 @@ struct qmps_ctx {
   int D = 0;
   int64_t max_batch = 0;
   hipStream_t stream = nullptr;
+  // Launch lanes (qmps_hazard.h): consecutive launches of the fused D = 4 energy kernel alternate between the context stream (lane 0) and
+  // a second compute stream (lane 1, created by the first such launch), so that a launch's first waves take the SIMD slots its
+  // predecessor's last waves have left.  Each of these launches is followed by an event and entered in lane_table; the next one waits for
+  // the other lane's newest launch that conflicts with it.  Everything else runs on the context stream behind bind(), which makes that
+  // stream wait for lane 1 (join_lanes) and notes that lane 1 has to wait for the context stream before its next launch (main_touched).
+  int lanes = 1;                            // QMPS_LAUNCH_LANES (qmps_knobs.h); 1: lane 1 is never used
+  hipStream_t lane_stream = nullptr;
+  hipStream_t launch_stream = nullptr;      // where the energy launch being issued goes: the context stream, but for a launch on lane 1
+  LaneTable lane_table;
+  hipEvent_t lane_ev[LaneTable::kLanes][LaneTable::kDepth] = {};
+  hipEvent_t lane_fork = nullptr;
+  int next_lane = 0;
+  bool main_touched = false;                // the context stream carries work that lane 1 does not follow yet
+  hipStream_t lane(int l) const { return l ? lane_stream : stream; }
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // ring of event pairs around the DOMINANT kernel of each qmps_energy_launch (read by qmps_kernel_time)
   static constexpr int kRing = 64;
@@ -242,6 +258,8 @@ struct qmps_ctx {
   bool acc_is[kCostSlots][kMaxGroup] = {};   // the position's cost lives in its accumulator (not yet a double in the ring)
   bool acc_dirty[kCostSlots][kMaxGroup] = {};  // the accumulator has been added to since it was last cleared
   bool acc_after_event[kCostSlots][kMaxGroup] = {};  // cleared by a memset on the compute stream: its finish kernel must wait for an event
+  int acc_lane[kCostSlots][kMaxGroup] = {};          // the lane launch that adds to the position: its finish kernel waits for that launch's
+  int64_t acc_seq[kCostSlots][kMaxGroup] = {};       //   event (acc_seq 0: no lane launch - the compute stream's order, as above)
   double acc_scale[kCostSlots][kMaxGroup] = {};
   int acc_shards[kCostSlots][kMaxGroup] = {};
   long long acc_expect[kCostSlots][kMaxGroup] = {};   // waves (tiles of 16 evaluations) that add to each term's shards
@@ -274,8 +292,8 @@ struct KernelTimer {
   bool on;     // this launch is timed
   int slot;    // its event pair in kev0 / kev1
   KernelTimer(qmps_ctx* ctx, bool timed) : c(ctx), on(timed), slot((int)(ctx->samples % qmps_ctx::kRing)) {}
-  hipError_t start() const { return on ? hipEventRecord(c->kev0[slot], c->stream) : hipSuccess; }
-  hipError_t extend() const { return on ? hipEventRecord(c->kev1[slot], c->stream) : hipSuccess; }
+  hipError_t start() const { return on ? hipEventRecord(c->kev0[slot], c->launch_stream) : hipSuccess; }      // (the launch's own lane)
+  hipError_t extend() const { return on ? hipEventRecord(c->kev1[slot], c->launch_stream) : hipSuccess; }
   hipError_t stop() { const hipError_t e = extend(); if (on && e == hipSuccess) c->samples++; return e; }
 };
 // energy and overlap launches: every timing_period-th launch outside a graph capture (qmps_set_kernel_timing_period)
@@ -289,7 +307,20 @@ inline int krylov_after() {
   return e ? atoi(e) : kKrylovAfter;
 }
 
+// bind: the device, and the context stream behind everything the lanes have been given (join_lanes) - the first call of every entry point
+// that touches device memory.  bind_device: the device alone, for the calls that order themselves against the lanes: qmps_energy_launch,
+// qmps_cost_launch.
 int bind(qmps_ctx* c);
+int bind_device(qmps_ctx* c);
+int join_lanes(qmps_ctx* c);
+// A launch of the fused D = 4 energy kernel on the next lane: lane_begin picks the lane (launch_stream) and makes it wait for what
+// conflicts with the footprint, lane_end enters the launch in the table and records its event; lane_wait makes another stream wait for
+// the launch (lane, seq), or for the whole lane once its event has been taken over.
+int lane_begin(qmps_ctx* c, const LaunchFootprint& f, int* lane);
+int lane_end(qmps_ctx* c, const LaunchFootprint& f, int lane, int64_t* seq);
+int lane_wait(qmps_ctx* c, hipStream_t waiter, int lane, int64_t seq);
+// the ring position an accumulating launch issued now would add to (ahead = 0) or clear for a later step (ahead = 2): setup_accumulator
+inline int acc_position(const qmps_ctx* c, int ahead) { return (int)((c->groups + ahead) % qmps_ctx::kCostSlots) * qmps_ctx::kMaxGroup + c->group_fill; }
 // after an overlap or evolve call: the energy path's resident environments, guesses, fixed points, pending cost and per-wave partial
 // sums no longer describe the buffers
 inline void forget_environments(qmps_ctx* c) { c->env.clear(); c->env_guessed.clear(); c->env_start.clear(); }
@@ -346,6 +377,9 @@ int ensure_tensors(qmps_ctx* c);
 // the summed-cost exchange (qmps_capi_cost.hip): an accumulating energy launch claims the ring position of the following
 // qmps_cost_launch; the current group of summed costs goes out in one all-reduce
 int setup_accumulator(qmps_ctx* c, qmps::LaneArgs& a, int64_t B, int64_t adds, int per_add);
+// qmps_energy_launch; may_overlap: the caller issues nothing on the context stream that depends on this launch without a bind() in
+// between (the entry point itself; the drivers, which launch their own kernels behind it, pass false)
+int energy_launch(qmps_ctx* c, int64_t B, int max_iter, double tol, int flags, bool may_overlap);
 int close_group(qmps_ctx* c);
 
 }  // namespace qmps_host

@@ -870,14 +870,19 @@ hipError_t direct_d4_wave_slots(int64_t* slots) {
 // for its whole life only swaps who runs alone; handed back there, the two waves of the last pair end together.  Timed against the
 // hand-back behind the acceptance step and against the younger half of every generation raised throughout, which gained nothing
 // (profiles/wave_pacing_ab.json).  A grid that fits in one generation has every wave resident from the start and raises nobody.
-// QMPS_WAVE_SLOTS (include/qmps_hip.h): 0 switches pacing off, a positive number stands for the slot count.
+// A launch on the launch lanes of a context (on_lanes) raises nobody: its last half generation does not run alone, the next launch's
+// first waves enter beside it, and raised waves held those back - two lanes with pacing measured slower than one lane, without it
+// 9 % faster (profiles/launch_lanes_ab.json).
+// QMPS_WAVE_SLOTS (include/qmps_hip.h): 0 switches pacing off, a positive number stands for the slot count, on the lanes as well.
 template <int ANS, bool WARM>
-hipError_t pace(LaneArgs& a, int64_t grid) {
+hipError_t pace(LaneArgs& a, int64_t grid, bool on_lanes) {
   a.prio_first = 0;
   a.prio_until = kPrioOff;
   int64_t slots = 0;
   if (const char* s = documented_switch("QMPS_WAVE_SLOTS")) {
     slots = atoll(s);
+  } else if (on_lanes) {
+    return hipSuccess;
   } else if (hipError_t e = direct_d4_wave_slots<ANS, WARM>(&slots)) {
     return e;
   }
@@ -888,26 +893,26 @@ hipError_t pace(LaneArgs& a, int64_t grid) {
 }
 
 template <int ANS, bool WARM>
-hipError_t launch_direct_d4(LaneArgs a, dim3 grid, hipStream_t st) {
-  if (hipError_t e = pace<ANS, WARM>(a, grid.x)) return e;
+hipError_t launch_direct_d4(LaneArgs a, dim3 grid, hipStream_t st, bool on_lanes) {
+  if (hipError_t e = pace<ANS, WARM>(a, grid.x, on_lanes)) return e;
   hipLaunchKernelGGL((energy_direct_d4_kernel<ANS, WARM>), grid, dim3(64), 0, st, a);
   return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_energy_direct_d4(const LaneArgs& a, hipStream_t st) {
+hipError_t launch_energy_direct_d4(const LaneArgs& a, hipStream_t st, bool on_lanes) {
   if (a.B <= 0) return hipSuccess;
   const dim3 grid((unsigned)((a.B + 15) / 16));
   const bool warm = a.r_in != nullptr;
-  if (a.ans_params == nullptr) return warm ? launch_direct_d4<-1, true>(a, grid, st) : launch_direct_d4<-1, false>(a, grid, st);
+  if (a.ans_params == nullptr) return warm ? launch_direct_d4<-1, true>(a, grid, st, on_lanes) : launch_direct_d4<-1, false>(a, grid, st, on_lanes);
   switch (a.ans_kind) {
     case QMPS_ANSATZ_SHALLOW_CNOT:
-      return warm ? launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT, true>(a, grid, st) : launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT, false>(a, grid, st);
+      return warm ? launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT, true>(a, grid, st, on_lanes) : launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT, false>(a, grid, st, on_lanes);
     case QMPS_ANSATZ_SHALLOW_QAOA:
-      return warm ? launch_direct_d4<QMPS_ANSATZ_SHALLOW_QAOA, true>(a, grid, st) : launch_direct_d4<QMPS_ANSATZ_SHALLOW_QAOA, false>(a, grid, st);
+      return warm ? launch_direct_d4<QMPS_ANSATZ_SHALLOW_QAOA, true>(a, grid, st, on_lanes) : launch_direct_d4<QMPS_ANSATZ_SHALLOW_QAOA, false>(a, grid, st, on_lanes);
     case QMPS_ANSATZ_SHALLOW_CNOT3:
-      return warm ? launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT3, true>(a, grid, st) : launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT3, false>(a, grid, st);
+      return warm ? launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT3, true>(a, grid, st, on_lanes) : launch_direct_d4<QMPS_ANSATZ_SHALLOW_CNOT3, false>(a, grid, st, on_lanes);
     default: return hipErrorInvalidValue;
   }
 }

@@ -152,7 +152,8 @@ hipError_t launch_energy_only_d4(const LaneArgs& a, hipStream_t st);
 // D = 4 plain power iteration, a quad per evaluation, persistent waves drawing evaluations from `counter` (zero at launch); writes r_out, iters, status
 hipError_t launch_env_power_d4(const LaneArgs& a, int* counter, int waves, hipStream_t st);
 // D = 4 DIRECT solve fused with the energies: one DPP quad per evaluation (qmps_direct.hip); partials: one per 16 items
-hipError_t launch_energy_direct_d4(const LaneArgs& a, hipStream_t st);
+// on_lanes: the launch is one of a context's launch lanes - its last waves share their SIMDs with a successor's first (no pacing)
+hipError_t launch_energy_direct_d4(const LaneArgs& a, hipStream_t st, bool on_lanes = false);
 
 // Whole D = 2 rotosolve run in one launch (restarts are independent): base [R][P] in/out, hist [n_sweeps][R] out
 struct RotoArgs {

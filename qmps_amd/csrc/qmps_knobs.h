@@ -21,4 +21,13 @@ inline const char* tuning_knob(const char* name) {
 #endif
 }
 
+// QMPS_LAUNCH_LANES (documented switch, read when a context is created): compute streams that consecutive launches of the fused
+// D = 4 energy kernel alternate between (qmps_hazard.h); 1 = every launch on the context stream.
+constexpr int kLaunchLanes = 2;
+inline int launch_lanes() {
+  const char* e = documented_switch("QMPS_LAUNCH_LANES");
+  const int n = e ? atoi(e) : kLaunchLanes;
+  return n >= 2 ? 2 : 1;
+}
+
 }  // namespace qmps

@@ -7,7 +7,7 @@
 
 using namespace qmps_host;
 
-// `reps` launches of qmps_energy_launch(B, max_iter, tol, flags) over the window - flags with QMPS_ENV_DIRECT; with
+// `reps` launches of qmps_energy_launch(B, max_iter, tol, flags) over the window, all on the context stream - flags with QMPS_ENV_DIRECT; with
 // QMPS_FLAG_ACCUMULATE_COST each followed by its qmps_cost_launch, as an optimiser step does - every wave stamping into the same
 // buffer (the last launch's record stays), HIP events round them all.  words: [(B + 15) / 16][kTimelineWords]; us_per_launch: nullable.
 extern "C" int qmps_wave_timeline(qmps_ctx* c, int64_t B, int max_iter, double tol, int flags, int reps, unsigned long long* words,
@@ -23,7 +23,7 @@ extern "C" int qmps_wave_timeline(qmps_ctx* c, int64_t B, int max_iter, double t
     HIP_TRY(hipMemsetAsync(d_tl, 0, bytes, c->stream));
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     for (int rep = 0; rep < reps; ++rep) {
-      if (int r = qmps_energy_launch(c, B, max_iter, tol, flags)) return r;
+      if (int r = energy_launch(c, B, max_iter, tol, flags, false)) return r;
       if (flags & QMPS_FLAG_ACCUMULATE_COST)
         if (int r = qmps_cost_launch(c, B)) return r;
     }
