@@ -664,7 +664,8 @@ int qmps_overlap_eval_ansatz(qmps_ctx* ctx, int64_t B, int kind, int n_params, c
  * per iterate instead of 2 n_params + 1.  params[T][n_params]: iterate t is compared with resident reference t.  The library
  * solves the RIGHT and the LEFT fixed point of the iterate's map (T(r) = eta r, T^+(y) = conj(eta) y; the left one by the power
  * method on the adjoint map y -> sum_s C_s^+ y Bm_s) and evaluates each of the 2 n_params neighbours params_t +- h e_k by
- *     eta' = <y, T'(r)> / <y, r>       (exact to second order in h: error O(h^2) ~ 1e-12 at h = 1e-6)
+ *     eta' = <y, T'(r)> / <y, r>       (exact to second order in h: the gradient is off its derivative by c h^2, c ~ 1 / gap - measured at
+ *                                       h = 1e-6: 1e-11 next to the reference, up to 4e-10 at |eta_2 / eta_1| = 0.998; tests/gradient_cases.py)
  * - one application of the neighbour's map instead of a power iteration.  f_out[T] = -sqrt|eta_t| (from the solve),
  * g_out[T][n_params] = (f(+h e_k) - f(-h e_k)) / 2h, status_out[T] = worst of the two solves (a status that is not usable beats
  * QMPS_STATUS_TIED, which beats 0).  QMPS_OVERLAP_WARM: both power iterations start from the fixed points the previous call left
@@ -674,8 +675,8 @@ int qmps_overlap_eval_ansatz(qmps_ctx* ctx, int64_t B, int kind, int n_params, c
  * QMPS_OVERLAP_TWO_SIDED_F: f_out comes from the two-sided quotient (not at a TIED iterate), f = -sqrt|<y, T(r)> / <y, r>| - its error is the
  * PRODUCT of the residuals of y and r, so the two solves may stop at tol ~ 1e-8 and still deliver eta to ~1e-16 (measured at
  * D = 16: |f - f_exact| < 1e-13 at tol = 1e-8, 16 power steps fewer than tol = 1e-12); the gradient inherits the residual to
- * first order (2e-8 at tol = 1e-8; central differences with h = 1e-6 carry 2e-10 of rounding themselves, scipy's own
- * forward differences ~1e-8).  D = 4, 8, 16; needs T (1 + 2 n_params) <= max_batch.  One synchronisation. */
+ * first order (amplification: tests/gradient_cases.py, `sens`; measured 2e-8 at tol = 1e-8; central differences with h = 1e-6 carry up to 6e-10 of
+ * rounding themselves, 2.7 2^-52 / h; scipy's own forward differences ~1e-8).  D = 4, 8, 16; needs T (1 + 2 n_params) <= max_batch.  One synchronisation. */
 #define QMPS_OVERLAP_TWO_SIDED_F 4
 int qmps_overlap_gradient(qmps_ctx* ctx, int64_t T, int kind, int n_params, const double* params, double h, int max_rounds, double tol,
                           int flags, double* f_out, double* g_out, int32_t* status_out);

@@ -312,12 +312,13 @@ __device__ __forceinline__ double overlap_tol2(const OverlapArgs& p, int64_t b) 
 }
 __device__ __forceinline__ bool overlap_skipped(const OverlapArgs& p, int64_t b) { return p.active != nullptr && p.active[p.group > 0 ? b / p.group : b] == 0; }
 __device__ __forceinline__ int64_t overlap_slot_offset(const OverlapArgs& p) { return p.slot_ptr != nullptr ? (int64_t)(*p.slot_ptr) * p.slot_stride : 0; }
-// results of one evaluation (called by ONE lane)
-__device__ __forceinline__ void overlap_store(const OverlapArgs& p, int64_t b, double eta_r, double eta_i, int rounds, int status) {
+// results of one evaluation (called by ONE lane); with_objective = false: a record that has no slot in f_out (the left solve's record
+// behind the B evaluations of a launch: f_out[B ..] belongs to the caller)
+__device__ __forceinline__ void overlap_store(const OverlapArgs& p, int64_t b, double eta_r, double eta_i, int rounds, int status, bool with_objective = true) {
   ((double2*)p.eta)[b] = make_double2(eta_r, eta_i);
   p.iters[b] = rounds;
   p.status[b] = status;
-  if (p.f_out != nullptr) p.f_out[b] = -__builtin_sqrt(__builtin_sqrt(eta_r * eta_r + eta_i * eta_i));
+  if (with_objective && p.f_out != nullptr) p.f_out[b] = -__builtin_sqrt(__builtin_sqrt(eta_r * eta_r + eta_i * eta_i));
   if (p.stats != nullptr) {
     // kOverlapStatShards sets of four counters (the host adds them up): 65 536 evaluations hammering ONE address cost 1.8 ms of
     // a 0.5 ms launch at D = 4

@@ -74,7 +74,10 @@ __global__ __launch_bounds__(256, 3) void overlap_square_d4_kernel(OverlapArgs p
     overlap_square_d4_item((const double2*)p.A + overlap_ref_index(p, b) * 32, (const double2*)p.Bt + b * 32, (const double2*)p.WW, sT, p.max_rounds, tol2,
                            eta_r, eta_i, rounds, status, mr, mi);
     if (lane == 0) overlap_store(p, b, eta_r, eta_i, rounds, status);
-    if (p.l_out != nullptr && lane == 0) overlap_store(p, b + p.B, eta_r, eta_i, rounds, status);      // (the left solve's record)
+    // (the left solve's record: eta, rounds, status and statistics.  No objective: f_out[B ..] holds the neighbours' objectives of
+    // qmps_overlap_gradient, and a skipped trajectory's must stay - this used to overwrite the first B of them, which the probes put
+    // right for every trajectory but a skipped one)
+    if (p.l_out != nullptr && lane == 0) overlap_store(p, b + p.B, eta_r, eta_i, rounds, status, false);
     if ((p.r_out != nullptr && p.adjoint) || p.l_out != nullptr) {
       // LEFT fixed point (T^+ y = conj(eta) y): M -> u v^+, so every row of M is a multiple of v^+; y = conj of the largest row
       void* lo = p.l_out != nullptr ? p.l_out : p.r_out;
